@@ -17,7 +17,13 @@ The one collective of the path (gradient all-reduce per optimizer step) belongs 
 `--ppo-epochs` (reported as `ppo_samples_per_s` in the same JSON line).
 
 One JSON line is printed by rank 0, with the `roofline` object of the dominant kernel (k_sim_step, timed live with
-HIP events on the launch stream) and the `cpu_baseline` object (CPU port of the same path on the host cores).
+HIP events on the launch stream).  A plain run does only what that line needs: set-up, burn-in and warm-up, the K timed
+steps, the line.  `--full` adds everything else the benchmark measures: the PPO epochs (`--ppo-epochs`), the live PMC
+passes behind `roofline.traffic`, the `cpu_baseline` object (CPU port of the same path on the host cores), the reference's
+CPU timings, the configs[0] line, the other workloads and the device state.
+
+    python bench.py --full                                  (the whole line; --no-* switches drop parts of it)
+    python bench.py --steps K --warmup W --dump-outputs DIR (after the timed steps: what the last step returned, DIR/<name>.npy)
 """
 import argparse
 import json
@@ -57,7 +63,12 @@ def parse():
                     "exists to exercise the multi-rank logic of this script with several ranks SHARING one GPU (tests on 1-GPU boxes)")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 5], help="BASELINE.json configs preset (1-based): 2 = SMPL 4096 envs single "
                     "clip (the bench line), 3 = 8192 envs + AMASS-sized synthetic library (--motion-clips, default 11313), 5 = H1 4096 envs")
-    ap.add_argument("--ppo-epochs", type=int, default=3, help="timed PPO epochs (rollout 32 steps + 48 optimizer steps: 6 mini-epochs x 8 minibatches); 0 = skip")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: PPO epochs, live PMC passes, CPU baseline and "
+                    "reference timings, configs[0] line, other workloads, device state (off: set-up, warm-up, timed steps, result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned (obs, reward, "
+                    "done, info arrays) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded sample of envs above that)")
+    ap.add_argument("--ppo-epochs", type=int, default=None, help="timed PPO epochs (rollout 32 steps + 48 optimizer steps: 6 mini-epochs x 8 minibatches); "
+                    "default 3 with --full, else 0; 0 = skip")
     ap.add_argument("--learning", default="im", help="learner config of the PPO part (phc/data/cfg/learning/*.yaml): im (the bench line: 1024-512 ReLU), "
                     "im_big / im_pnn_big (the reference's flagship 2048-1536-1024-1024-512-512 SiLU networks; im_pnn* also selects env=env_im_pnn)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -383,6 +394,40 @@ def device_state(dev):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 * 2 ** 20   # under 64 MB (decimal) with the .npy headers and the sample index
+
+
+def dump_outputs(out_dir, result, num_envs):
+    """What one timed step hands its caller -- `(obs, reward, done, info)` of VecTaskPythonWrapper.step -- as <out_dir>/<name>.npy in float32
+    (integer and boolean flags converted), so that two builds can be compared output for output.  Above DUMP_LIMIT_BYTES in all, the same
+    fixed, seeded sample of env rows is taken from every per-env array (and written as `sample_env_ids.npy`)."""
+    arrays = {}
+
+    def collect(name, x):
+        if isinstance(x, dict):
+            for k, v in x.items():
+                collect(f"{name}_{k}", v)
+        elif isinstance(x, torch.Tensor):
+            arrays[name] = x.detach().float().cpu().numpy()
+        elif isinstance(x, np.ndarray):
+            arrays[name] = x.astype(np.float32)
+    obs, rew, done, info = result
+    collect("obs", obs)
+    collect("reward", rew)
+    collect("done", done)
+    collect("info", info)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = int(num_envs * DUMP_LIMIT_BYTES // total) - 1
+        ids = np.sort(np.random.default_rng(0).choice(num_envs, size=keep, replace=False))
+        arrays = {k: (a[ids] if a.ndim and a.shape[0] == num_envs else a) for k, a in arrays.items()}
+        arrays["sample_env_ids"] = ids.astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(arrays)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU (RCCL)."""
     import socket
@@ -403,6 +448,8 @@ def spawn_ranks(n):
 
 def main():
     args = parse()
+    if args.ppo_epochs is None:
+        args.ppo_epochs = 3 if args.full else 0
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -508,11 +555,13 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        env_step(events[k], events_post[k])
+        last = env_step(events[k], events_post[k])
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # before anything else runs on the task (the PPO epochs of --full step it further)
+        dump_outputs(args.dump_outputs, last, N)
     per_rank = [elapsed]
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -543,7 +592,7 @@ def main():
         bytes_per_launch = (aba_bytes * nsub + pub_bytes) * N
         traffic, traffic_src = None, None  # HBM bytes per launch of the stepper from the PMC counters
         per, post_traffic, post_src, sq = None, None, None, None
-        if world == 1 and not args.no_pmc and not os.environ.get("PHC_BENCH_CHILD"):
+        if args.full and world == 1 and not args.no_pmc and not os.environ.get("PHC_BENCH_CHILD"):
             tail = ["--envs", str(args.envs), "--robot", args.robot, "--lane-mapping", str(args.lane_mapping), "--actions", args.actions,
                     "--motion-clips", str(args.motion_clips), "--self-collision", str(args.self_collision)] + [x for kv in args.solver for x in ("--solver", kv)]
             # four child passes: HBM read / write traffic (all kernels), then the SQ counters behind the VALU roofline of the stepper
@@ -614,7 +663,7 @@ def main():
                                             "algorithmic_bytes_per_launch": post_bytes}
         if ppo is not None:
             out.update(ppo)
-        if world == 1 and not args.no_cpu_baseline and args.robot == "smpl":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.robot == "smpl":
             out["cpu_baseline"] = cpu_baseline()
             ref = cpu_reference()
             if ref is not None:
@@ -626,14 +675,14 @@ def main():
                     out["config0"] = {"error": repr(e)}
         if cfg3 is not None:
             out["config3_motion_library"] = cfg3
-        if (world == 1 and not args.no_other_workloads and not os.environ.get("PHC_BENCH_CHILD") and args.config == 2 and args.robot == "smpl"
+        if (args.full and world == 1 and not args.no_other_workloads and not os.environ.get("PHC_BENCH_CHILD") and args.config == 2 and args.robot == "smpl"
                 and args.actions == "random" and args.envs == 4096):
             out["other_workloads"] = other_workloads()
         out["per_rank"] = [{"rank": r, "elapsed_s": e, "env_steps_per_s": N * args.steps / e} for r, e in enumerate(per_rank)]
         out["actions"] = args.actions
         if args.solver:
             out["solver_overrides"] = list(args.solver)
-        if not os.environ.get("PHC_BENCH_CHILD"):
+        if args.full and not os.environ.get("PHC_BENCH_CHILD"):
             out["device"] = device_state(dev)
         out["envs_within_5_steps_of_a_reset"] = resets
         out["protocol_burn_in_steps"] = BURN_IN   # untimed, before the W warm-up steps: desynchronises the resets after env.reset()

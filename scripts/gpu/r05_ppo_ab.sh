@@ -5,7 +5,7 @@
 O=gpurun_out/${1:-r05_ppo_ab}
 mkdir -p $O
 timeout 900 python -m pytest tests/test_stepper_options.py tests/test_learn_gpu.py tests/test_dynamics.py tests/test_h1.py -m gpu -q -x > $O/pytest.log 2>&1; tail -3 $O/pytest.log
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-other-workloads"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-other-workloads"
 for rep in 1 2 3; do
   $B > $O/ppo_new_$rep.json 2>> $O/err.log
   PHC_NO_DEFER_COLSUM=1 PHC_NO_DIRECT_DD_BIAS=1 PHC_AMD_LIB=$PWD/phc_amd/_obj/libphc_amd_nov8.so $B > $O/ppo_old_$rep.json 2>> $O/err.log

@@ -5,7 +5,7 @@ O=gpurun_out/${1:-r05_ref}
 mkdir -p $O
 ls oracle/_ref | head -3 > $O/ref_ls.txt 2>&1
 timeout 900 python -m pytest tests/test_reference_direct_gpu.py -m gpu -q -x -s > $O/pytest_ref.log 2>&1; tail -5 $O/pytest_ref.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.err
 python - <<PY
 import json
 d = json.load(open('$O/bench_default.json'))

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for round in 1 2; do
 for tag in base pkmat pkops pkboth; do
   if [ $tag = base ]; then unset PHC_AMD_LIB; else export PHC_AMD_LIB=$PWD/phc_amd/_obj/libphc_amd_$tag.so; fi
-  rocprofv3 --kernel-trace --stats -d /tmp/prof_${tag}_$round -o b -- python bench.py --steps 300 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/bench_${tag}_$round.json 2> $O/err_${tag}_$round.log
+  rocprofv3 --kernel-trace --stats -d /tmp/prof_${tag}_$round -o b -- python bench.py --full --steps 300 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/bench_${tag}_$round.json 2> $O/err_${tag}_$round.log
   echo "$tag round $round: $(python profiles/summarize_rocpd.py $(find /tmp/prof_${tag}_$round -name '*.db' | head -1) | grep k_sim_step | cut -c1-110)"
 done; done
 for tag in pkboth; do

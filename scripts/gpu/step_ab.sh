@@ -18,7 +18,7 @@ TESTS=""; LIBS="default"; SOLVERS=""; ROBOTS="smpl"; REPS=2; EXTRA=""; PROBE=""
 while getopts "t:l:s:r:n:b:p:" o; do case $o in t) TESTS=$OPTARG;; l) LIBS=$OPTARG;; s) SOLVERS=$OPTARG;; r) ROBOTS=$OPTARG;; n) REPS=$OPTARG;; b) EXTRA=$OPTARG;; p) PROBE=$OPTARG;; esac; done
 mkdir -p $O
 if [ -n "$TESTS" ]; then timeout 1500 python -m pytest $TESTS -m gpu -q -x > $O/pytest.log 2>&1; tail -3 $O/pytest.log; fi
-B="python bench.py --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads $EXTRA"
+B="python bench.py --full --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads $EXTRA"
 IFS=';' read -ra SETS <<< "${SOLVERS};"
 [ ${#SETS[@]} -eq 0 ] && SETS=("")
 for rep in $(seq 1 $REPS); do for robot in $ROBOTS; do for lib in $LIBS; do for set in "${SETS[@]}"; do

@@ -3,7 +3,7 @@
 O=gpurun_out/sweep
 mkdir -p $O
 for n in 512 1024 2048 4096 8192 16384 32768; do
-  python bench.py --envs $n --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --steps 200 --warmup 20 > $O/envs_$n.json 2>> $O/err.log
+  python bench.py --full --envs $n --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --steps 200 --warmup 20 > $O/envs_$n.json 2>> $O/err.log
 done
 python - <<'PY'
 import json, glob

@@ -3,13 +3,13 @@
 O=gpurun_out/${1:-r2r}
 mkdir -p $O
 if [ -z "$SKIP_PYTEST" ]; then python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log; fi
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.err
-python bench.py --actions tracking --no-cpu-baseline --no-pmc --ppo-epochs 0 > $O/bench_tracking.json 2>> $O/bench_default.err
-python bench.py --config 5 --ppo-epochs 0 --no-cpu-baseline --no-pmc > $O/bench_h1.json 2>> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.err
+python bench.py --full --actions tracking --no-cpu-baseline --no-pmc --ppo-epochs 0 > $O/bench_tracking.json 2>> $O/bench_default.err
+python bench.py --full --config 5 --ppo-epochs 0 --no-cpu-baseline --no-pmc > $O/bench_h1.json 2>> $O/bench_default.err
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench -- python bench.py --steps 200 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc > $O/prof_bench.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench -- python bench.py --full --steps 200 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc > $O/prof_bench.json 2> $O/prof.err
 python profiles/summarize_rocpd.py $(find /tmp/prof -name '*.db' | head -1) > $O/env_step_kernel_stats.txt
-rocprofv3 --kernel-trace --stats -d /tmp/prof2 -o ppo -- python bench.py --steps 20 --warmup 5 --ppo-epochs 1 --no-cpu-baseline --no-pmc > $O/prof_ppo.json 2>> $O/prof.err
+rocprofv3 --kernel-trace --stats -d /tmp/prof2 -o ppo -- python bench.py --full --steps 20 --warmup 5 --ppo-epochs 1 --no-cpu-baseline --no-pmc > $O/prof_ppo.json 2>> $O/prof.err
 python profiles/summarize_rocpd.py $(find /tmp/prof2 -name '*.db' | head -1) > $O/ppo_epoch_kernel_stats.txt
 bash profiles/collect_pmc.sh > $O/pmc_traffic.txt 2>> $O/prof.err
 python - <<PY

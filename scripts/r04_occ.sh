@@ -4,7 +4,7 @@ set -x
 OUT=gpurun_out/r04_occ
 mkdir -p $OUT
 for n in 4096 8192 12288; do for lm in 1 3; do
-  python bench.py --envs $n --lane-mapping $lm --steps 200 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $OUT/envs${n}_lm${lm}.json 2> $OUT/envs${n}_lm${lm}.err
+  python bench.py --full --envs $n --lane-mapping $lm --steps 200 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $OUT/envs${n}_lm${lm}.json 2> $OUT/envs${n}_lm${lm}.err
 done; done
 python - <<'P'
 import json,glob

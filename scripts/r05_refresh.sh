@@ -6,19 +6,19 @@ O=gpurun_out/${1:-r5r}
 mkdir -p $O
 if [ -z "$SKIP_PYTEST" ]; then timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log; fi
 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2>> $O/bench_default.err
-python bench.py --actions tracking --no-cpu-baseline --no-pmc --ppo-epochs 0 --no-other-workloads > $O/bench_tracking.json 2>> $O/bench_default.err
-python bench.py --config 5 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/bench_h1.json 2>> $O/bench_default.err
-python bench.py --config 5 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --solver inertia_lag=1 > $O/bench_h1_lag.json 2>> $O/bench_default.err
-python bench.py --robot g1 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/bench_g1.json 2>> $O/bench_default.err
-python bench.py --robot g1 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --solver inertia_lag=1 > $O/bench_g1_lag.json 2>> $O/bench_default.err
-python bench.py --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --solver inertia_lag=1 > $O/bench_lag.json 2>> $O/bench_default.err
-if [ -n "$WITH_CONFIG3" ]; then python bench.py --config 3 --ppo-epochs 0 --no-cpu-baseline --no-pmc > $O/bench_config3.json 2>> $O/bench_default.err; fi
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.json 2>> $O/bench_default.err
+python bench.py --full --actions tracking --no-cpu-baseline --no-pmc --ppo-epochs 0 --no-other-workloads > $O/bench_tracking.json 2>> $O/bench_default.err
+python bench.py --full --config 5 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/bench_h1.json 2>> $O/bench_default.err
+python bench.py --full --config 5 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --solver inertia_lag=1 > $O/bench_h1_lag.json 2>> $O/bench_default.err
+python bench.py --full --robot g1 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/bench_g1.json 2>> $O/bench_default.err
+python bench.py --full --robot g1 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --solver inertia_lag=1 > $O/bench_g1_lag.json 2>> $O/bench_default.err
+python bench.py --full --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads --solver inertia_lag=1 > $O/bench_lag.json 2>> $O/bench_default.err
+if [ -n "$WITH_CONFIG3" ]; then python bench.py --full --config 3 --ppo-epochs 0 --no-cpu-baseline --no-pmc > $O/bench_config3.json 2>> $O/bench_default.err; fi
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench -- python bench.py --steps 200 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/prof_bench.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench -- python bench.py --full --steps 200 --warmup 20 --ppo-epochs 0 --no-cpu-baseline --no-pmc --no-other-workloads > $O/prof_bench.json 2> $O/prof.err
 python profiles/summarize_rocpd.py $(find /tmp/prof -name '*.db' | head -1) > $O/env_step_kernel_stats.txt
-rocprofv3 --kernel-trace --stats -d /tmp/prof2 -o ppo -- python bench.py --steps 20 --warmup 5 --ppo-epochs 1 --no-cpu-baseline --no-pmc --no-other-workloads > $O/prof_ppo.json 2>> $O/prof.err
+rocprofv3 --kernel-trace --stats -d /tmp/prof2 -o ppo -- python bench.py --full --steps 20 --warmup 5 --ppo-epochs 1 --no-cpu-baseline --no-pmc --no-other-workloads > $O/prof_ppo.json 2>> $O/prof.err
 python profiles/summarize_rocpd.py $(find /tmp/prof2 -name '*.db' | head -1) > $O/ppo_epoch_kernel_stats.txt
 python profiles/dump_step.py $(find /tmp/prof2 -name '*.db' | head -1) > $O/ppo_optimizer_step_kernels.txt 2>> $O/prof.err || true
 bash profiles/collect_pmc.sh > $O/pmc_traffic.txt 2>> $O/prof.err

@@ -99,26 +99,45 @@ def test_model_compiler_matches_reference_skeleton(golden):
     assert scale[m.body_names[1:].index("L_Knee") * 3 + 1] == 5
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/phc/data/cfg"), reason="reference checkout not present")
-def test_model_asset_is_what_the_compiler_produces_from_the_reference_mjcf():
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def _robot_mjcf_with_meshes(robot, xml, tmp_path):
+    """The reference's robot MJCF (tests/golden/ref_robot/) next to a meshes/ folder of binary STL files rebuilt from the stored vertices
+    (tests/golden/ref_robot_meshes_<robot>.npz: each mesh's convex-hull boundary vertices in their STL order, oracle/gen_golden_ref_fixtures.py)."""
+    import shutil
+    d = tmp_path / robot
+    (d / "meshes").mkdir(parents=True)
+    shutil.copyfile(os.path.join(GOLDEN, "ref_robot", robot, xml), d / xml)
+    with np.load(os.path.join(GOLDEN, f"ref_robot_meshes_{robot}.npz")) as z:
+        for name in z.files:
+            v = z[name].astype("<f4")
+            v = np.concatenate([v, np.repeat(v[-1:], (-len(v)) % 3, 0)])     # whole triangles: the last vertex repeated
+            rec = np.zeros(len(v) // 3, dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("a", "<u2")]))
+            rec["v"] = v.reshape(-1, 3, 3)
+            (d / "meshes" / name).write_bytes(bytes(80) + np.uint32(len(rec)).tobytes() + rec.tobytes())
+    return str(d / xml)
+
+
+def test_model_asset_is_what_the_compiler_produces_from_the_reference_mjcf(tmp_path):
     from phc_amd.model import ArticulationModel, compile_mjcf, load_model
-    a = ArticulationModel(compile_mjcf("/root/reference/phc/data/assets/mjcf/smpl_0_humanoid.xml"))
+    mjcf = os.path.join(GOLDEN, "ref_mjcf")
+    a = ArticulationModel(compile_mjcf(os.path.join(mjcf, "smpl_0_humanoid.xml")))
     b = load_model("smpl_humanoid")
     for x, y in zip(a.pack(), b.pack()):
         np.testing.assert_array_equal(x, y)
     # the gender assets (per-env shapes: the reference's fallback, humanoid.py:748) and the y-up one (has_upright_start False)
     for name, xml in (("smpl_0_humanoid", "smpl_0_humanoid.xml"), ("smpl_1_humanoid", "smpl_1_humanoid.xml"), ("smpl_2_humanoid", "smpl_2_humanoid.xml"),
                       ("smpl_yup_humanoid", "smpl_humanoid.xml")):
-        a = ArticulationModel(compile_mjcf("/root/reference/phc/data/assets/mjcf/" + xml))
+        a = ArticulationModel(compile_mjcf(os.path.join(mjcf, xml)))
         for x, y in zip(a.pack(), load_model(name).pack()):
             np.testing.assert_array_equal(x, y)
-    for name, xml in (("h1_humanoid", "unitree_h1/h1.xml"), ("g1_humanoid", "unitree_g1/g1.xml")):   # robots: mesh hulls from the shipped STLs
-        a = ArticulationModel(compile_mjcf("/root/reference/phc/data/assets/robot/" + xml))
+    for name, robot, xml in (("h1_humanoid", "h1", "h1.xml"), ("g1_humanoid", "g1", "g1.xml")):   # robots: mesh hulls from the shipped STLs
+        a = ArticulationModel(compile_mjcf(_robot_mjcf_with_meshes(robot, xml, tmp_path)))
         for x, y in zip(a.pack(), load_model(name).pack()):
             np.testing.assert_array_equal(x, y)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/phc/data/cfg"), reason="reference checkout not present")
 @pytest.mark.parametrize("ov", [[], ["learning=im_big"], ["learning=im_pnn", "env=env_im_pnn"], ["learning=im_pnn_big"],
                                 ["learning=im_mcp", "env=env_im_getup_mcp"], ["env=env_vr"], ["robot=smpl_humanoid_shape"],
                                 ["robot=unitree_h1", "env=env_im_h1_phc", "sim=robot_sim", "control=robot_control"],
@@ -142,7 +161,7 @@ def test_builtin_config_equals_reference_yaml_tree(ov):
         return bad
 
     ours = compose(ov)
-    ref = compose(ov, cfg_dir="/root/reference/phc/data/cfg")
+    ref = compose(ov, cfg_dir=os.path.join(GOLDEN, "ref_cfg"))      # the reference's yaml tree, as is (oracle/gen_golden_ref_fixtures.py)
     assert diff(ours, ref) == []
     assert isinstance(ref.learning.params.config.learning_rate, float)
     assert compose(["env.num_envs=17", "+env.foo=[1,2]"]).env.num_envs == 17

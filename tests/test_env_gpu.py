@@ -672,7 +672,7 @@ def test_bench_multi_rank_logic_ranks_sharing_one_gpu(world):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     envs = 512 if world == 2 else 256
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--envs", str(envs), "--steps", "20", "--warmup", "5",
-                        "--ppo-epochs", "2", "--no-cpu-baseline", "--no-pmc"], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
+                        "--ppo-epochs", "2", "--full", "--no-cpu-baseline", "--no-pmc"], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1, r.stdout[-2000:]            # rank 0 alone prints

@@ -70,25 +70,23 @@ def small_cfg():
     return cfg
 
 
-def test_running_mean_std_matches_reference():
+def test_running_mean_std_matches_reference(golden):
+    """Outputs and moments equal the reference's own RunningMeanStd on the same seeded inputs (tests/golden/ref_running_mean_std.npz,
+    oracle/gen_golden_ref_fixtures.py)."""
+    g = golden("ref_running_mean_std")
     torch.manual_seed(0)
     ours = RunningMeanStd((7,))
     ours.train()
-    ref = None
-    if os.path.isdir("/root/reference"):
-        import ref_shim
-        ref = ref_shim.ref_module("phc.utils.running_mean_std").RunningMeanStd((7,))
-        ref.train()
     xs = [torch.randn(50, 7) * (i + 1) + i for i in range(4)]
-    for x in xs:
+    assert torch.equal(torch.stack(xs), torch.from_numpy(g["xs"]))
+    for x, y_ref in zip(xs, g["ys"]):
         y = ours(x)
-        if ref is not None:
-            assert torch.equal(y, ref(x))
+        assert torch.equal(y, torch.from_numpy(y_ref))
     assert ours.running_mean.dtype == torch.float64 and ours.count.item() == 201
     allx = torch.cat(xs).double()
     np.testing.assert_allclose(ours.running_mean.numpy(), allx.sum(0).numpy() / 201, rtol=1e-4, atol=1e-5)  # count starts at 1 with mean 0; batch moments are fp32
-    if ref is not None:
-        assert torch.equal(ours.running_mean, ref.running_mean) and torch.equal(ours.running_var, ref.running_var)
+    assert torch.equal(ours.running_mean, torch.from_numpy(g["running_mean"])) and torch.equal(ours.running_var, torch.from_numpy(g["running_var"]))
+    assert torch.equal(ours.count, torch.from_numpy(g["count"]))
     ours.eval()
     m = ours.running_mean.clone()
     y = ours(xs[0])
@@ -301,29 +299,22 @@ def test_first_write_protocol_of_the_flat_bucket():
     assert b.shadow is None and lin.weight.grad.data_ptr() == b.flat.data_ptr()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/phc/learning/replay_buffer.py"), reason="reference checkout not present")
-def test_replay_buffer_equals_the_reference_class():
+def test_replay_buffer_equals_the_reference_class(golden):
     """P9: the same store / sample sequence (wrap-around stores, sampling before and after the buffer fills, index re-shuffles) through
-    the reference's own `ReplayBuffer` (phc/learning/replay_buffer.py, pure torch: imported as is) and through ours, same torch seed:
-    identical storage, identical samples."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("ref_replay_buffer", "/root/reference/phc/learning/replay_buffer.py")
-    ref_mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref_mod)
-    outs = []
-    for cls in (ref_mod.ReplayBuffer, ReplayBuffer):
-        torch.manual_seed(42)
-        rb = cls(37, "cpu")
-        g = torch.Generator().manual_seed(1)
-        seq = []
-        for n_store, n_sample in ((10, 5), (20, 16), (15, 30), (37, 8), (3, 50), (9, 37)):
-            rb.store({"amp_obs": torch.randn(n_store, 4, generator=g)})
-            seq.append(rb.sample(n_sample)["amp_obs"].clone())
-        outs.append((rb._data_buf["amp_obs"].clone(), seq, rb.get_total_count(), rb._head))
-    (da, sa, ca, ha), (db, sb, cb, hb) = outs
-    assert ca == cb and ha == hb and torch.equal(da, db)
-    for x, y in zip(sa, sb):
-        assert torch.equal(x, y)
+    ours and, recorded in tests/golden/ref_replay_buffer.npz, through the reference's own `ReplayBuffer` (phc/learning/replay_buffer.py,
+    oracle/gen_golden_ref_fixtures.py), same torch seed: identical storage, identical samples."""
+    g_ref = golden("ref_replay_buffer")
+    torch.manual_seed(42)
+    rb = ReplayBuffer(37, "cpu")
+    g = torch.Generator().manual_seed(1)
+    seq = []
+    for n_store, n_sample in ((10, 5), (20, 16), (15, 30), (37, 8), (3, 50), (9, 37)):
+        rb.store({"amp_obs": torch.randn(n_store, 4, generator=g)})
+        seq.append(rb.sample(n_sample)["amp_obs"].clone())
+    assert rb.get_total_count() == int(g_ref["total_count"]) and rb._head == int(g_ref["head"])
+    assert torch.equal(rb._data_buf["amp_obs"], torch.from_numpy(g_ref["data"]))
+    for i, x in enumerate(seq):
+        assert torch.equal(x, torch.from_numpy(g_ref[f"sample_{i}"]))
 
 
 def test_train_checkpoint_cadence_and_termination_history_restore(tmp_path):

@@ -394,23 +394,21 @@ def test_split_bf16_actor_brings_the_actor_gradients_to_the_reference(golden, fi
     _check_step(agent, g, info, rtol_loss=8e-2, grad_rtol=0.6, grad_atol=1e-4, param_atol=4.1e-5, stats_rtol=1e-7, skip=("actor_loss", "kl", "actor_mlp", "a2c_network.mu"))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/phc"), reason="reference checkout not present")
-def test_bypass_mlp_loads_the_reference_class_state_dict():
-    """env.mlp_bypass (humanoid_im_mcp.py:31-38,83-84): a state dict written by the reference's own `phc.learning.mlp.MLP` loads into
-    BypassMLP (bare or under `model_state_dict`) and gives the same actions."""
+def test_bypass_mlp_loads_the_reference_class_state_dict(golden):
+    """env.mlp_bypass (humanoid_im_mcp.py:31-38,83-84): a state dict laid out as the reference's own `phc.learning.mlp.MLP` writes it loads
+    into BypassMLP (bare or under `model_state_dict`) and gives the reference class's actions (tests/golden/ref_bypass_mlp.npz: its keys,
+    shapes, and its actions with seeded weights loaded, oracle/gen_golden_ref_fixtures.py)."""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "oracle"))
-    import ref_shim
-    ref_shim.install()
-    RefMLP = ref_shim.ref_module("phc.learning.mlp").MLP
+    from gen_golden_ref_fixtures import seeded_state_dict
     from phc_amd.env.tasks.humanoid_im_mcp import load_bypass_mlp
-    torch.manual_seed(4)
-    ref = RefMLP(input_dim=934, output_dim=69, units=[2048, 1024, 512], activation="silu")
-    x = torch.randn(5, 934)
-    want = ref(x)
-    for ck in (ref.state_dict(), {"model_state_dict": ref.state_dict(), "epoch": 3}):
+    g = golden("ref_bypass_mlp")
+    keys = [str(k) for k in g["keys"]]
+    sd = seeded_state_dict(keys, g["shapes"], int(g["seed"]))
+    x, want = torch.from_numpy(g["x"]), torch.from_numpy(g["actions"])
+    for ck in (sd, {"model_state_dict": sd, "epoch": 3}):
         mine = load_bypass_mlp(ck, 934, 69)
-        assert list(mine.state_dict()) == list(ref.state_dict())
+        assert list(mine.state_dict()) == keys
         assert torch.equal(mine(x), want) and not any(p.requires_grad for p in mine.parameters())
 
 

@@ -138,13 +138,12 @@ def test_poselib_rotation_kat(golden):
     np.testing.assert_allclose(ax, g["diff_axis"], atol=1e-9)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/poselib/poselib/skeleton/tests/ant.xml"), reason="reference fixture only exists in the build container")
 def test_model_compiler_on_the_reference_ant_fixture(golden):
     """compile_mjcf on the reference's only skeleton fixture (ant.xml: fixed bodies, single hinges, degrees, no free joint) gives the
     tree SkeletonTree.from_mjcf reads from it."""
     from phc_amd.model import compile_mjcf
     g = golden("poselib_kat")
-    m = compile_mjcf("/root/reference/poselib/poselib/skeleton/tests/ant.xml")
+    m = compile_mjcf(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_mjcf", "ant.xml"))   # poselib's fixture, as is
     assert m["body_names"] == list(g["ant_names"])
     np.testing.assert_array_equal(np.array(m["parent"]), g["ant_parents"])
     np.testing.assert_allclose(np.array(m["local_translation"]), g["ant_local_translation"], atol=1e-7)
