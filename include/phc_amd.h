@@ -477,9 +477,11 @@ int32_t phc_linear1_backward(const void* x, const void* w, const void* gy, int64
 /* P9: gradient clipping + optimizer step on the flat fp32 parameter (phc/learning/amp_agent.py:669-676: `clip_grad_norm_(grad_norm)`
  * then `optimizer.step()` with torch.optim.Adam): grad *= min(1, max_norm / (|grad| + 1e-6)) in place (max_norm <= 0: no clipping),
  * then Adam with L2 weight decay; `step` is the 1-based step count (bias corrections computed on the host in fp64).
- * grad_norm_out (optional, device) receives |grad| before clipping; param_bf16 (optional, [n] bf16) receives the updated parameter
- * rounded to bf16 -- the copy the next step's GEMMs read.  step_device (optional, device int64): incremented by one and used for the
- * bias corrections instead of `step` -- for launches replayed from a captured hipGraph, whose by-value arguments are frozen.
+ * grad_norm_out (optional, device) receives |grad| before clipping (written when max_norm > 0); param_bf16 (optional, [n] bf16) receives the
+ * updated parameter rounded to bf16 -- the copy the next step's GEMMs read.  step_device (optional, device int64): incremented by one and used
+ * for the bias corrections instead of `step` -- for launches replayed from a captured hipGraph, whose by-value arguments are frozen.
+ * Alignment: param, grad, exp_avg and exp_avg_sq need only be 4-byte aligned and param_bf16 2-byte aligned (offset views are fine); 16-byte
+ * aligned fp32 arrays with an 8-byte aligned param_bf16 take the vectorised path, with the same per-element arithmetic.
  * workspace: phc_adam_workspace() bytes. */
 int64_t phc_adam_workspace(void);
 int32_t phc_adam_clip_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,

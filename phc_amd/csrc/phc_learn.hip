@@ -267,10 +267,13 @@ __global__ __launch_bounds__(AD_BLOCK) void k_sumsq(const float* __restrict__ g,
     if (step_dev && blockIdx.x == 0 && threadIdx.x == 0) *step_dev += 1;   // device-resident step count (graph replays): read by k_adam
     const int64_t base = ((int64_t)blockIdx.x * AD_BLOCK + threadIdx.x) * 4;
     const int64_t stride = (int64_t)gridDim.x * AD_BLOCK * 4;
+    const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;   // (an offset view of the gradient: scalar loads, the same sums)
     float a = 0.f;
     for (int64_t i = base; i < n; i += stride) {
         if (i + 3 < n) {
-            const float4 v = *reinterpret_cast<const float4*>(g + i);
+            float4 v;
+            if (vec) v = *reinterpret_cast<const float4*>(g + i);
+            else v = make_float4(g[i], g[i + 1], g[i + 2], g[i + 3]);
             a += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
         } else {
             for (int64_t k = i; k < n; ++k) a += g[k] * g[k];
@@ -350,7 +353,8 @@ __global__ __launch_bounds__(AD_BLOCK) void k_adam(float* __restrict__ p, float*
         }
         return;
     }
-    for (int64_t i = i0; i < n; ++i) {
+    const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;   // this lane's four elements (buffers that are not 16-byte aligned, the ragged tail)
+    for (int64_t i = i0; i < i1; ++i) {
         float go, po, mn, vn;
         one(g[i], p[i], m[i], v[i], go, po, mn, vn);
         g[i] = go; m[i] = mn; v[i] = vn; p[i] = po;
