@@ -101,7 +101,7 @@ class deferred_colsums:
 
 
 def _defer(out):
-    return _DEFER[0] > 0 and out is not None and out.is_cuda and not os.environ.get("PHC_NO_DEFER_COLSUM")
+    return _DEFER[0] > 0 and out is not None and out.is_cuda
 
 
 def _pend(ws, out, nchunks, cols, accumulate=0):
@@ -182,7 +182,7 @@ def _match_cols(wb, xb):
 def _pad_like(gx, x):
     """An input gradient computed against the UNPADDED weight (outside FlatGradBucket.shadow_scope() the bf16 copy of a K-padded first layer
     has K columns) brought to the K-padded input's width: the pad columns of the input are constants (zero), their gradient is zero."""
-    if gx is None or gx.dim() != 2 or x.dim() != 2 or gx.shape[1] >= x.shape[1]:
+    if x is None or gx.dim() != 2 or x.dim() != 2 or gx.shape[1] >= x.shape[1]:
         return gx
     return torch.nn.functional.pad(gx, (0, x.shape[1] - gx.shape[1]))
 
@@ -241,21 +241,53 @@ def _wgrad_into(weight, gy, xb):
     return None
 
 
+def _bf16_params(weight, bias, cast=True):
+    """The bf16 operands of a layer: inside FlatGradBucket.shadow_scope() the copies the optimizer kernel keeps up to date, elsewhere
+    casts of the parameters (`cast=False`: None)."""
+    live = getattr(weight, "_shadow_live", None)
+    if live is not None and live[0]:
+        return weight._bf16_shadow, bias._bf16_shadow
+    return (weight.to(torch.bfloat16), bias.to(torch.bfloat16)) if cast else None
+
+
+def _relu_mask(g, y, out=None):
+    """g where y > 0 else 0 (the ReLU's backward), optionally into `out`."""
+    if out is None:
+        return torch.ops.aten.threshold_backward(g, y, 0.0)
+    return torch.ops.aten.threshold_backward.grad_input(g, y, 0.0, grad_input=out)
+
+
+def _linear_grads(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like=None):
+    """First-order backward of a bf16 layer y = x W^T + b (and of the ReLU behind it when its output `y` is given) -> (gz, gx, gw, gb):
+    gz = gy masked by y > 0, gx = gz W (brought to the width of `pad_like` when given, see _pad_like), gw = gz^T xb, gb = 1^T gz;
+    gw / gb are None when they were stored or added in the parameter's bucket gradient (_wgrad_into, _first_write)."""
+    gy = gy.contiguous()
+    gb = direct = None       # direct: the bias gradient goes straight into the bucket (None: not decided yet)
+    if y is not None:
+        if need_gb and gy.dtype == torch.bfloat16:
+            # ReLU mask and bias gradient in ONE pass over the output gradient (phc_colsum_relu_bf16)
+            direct = _first_write(bias)
+            gy, gb = colsum_relu_bf16(gy, y, out=bias.grad if direct else None)
+        else:
+            gy = _relu_mask(gy, y)
+    gx = _pad_like((gy @ wb).to(x_dtype), pad_like) if need_gx else None
+    gw = _wgrad_into(weight, gy, xb)
+    if need_gb and direct is None:
+        direct = _first_write(bias)
+        gb = colsum_bf16(gy, out=bias.grad if direct else None)
+    return gy, gx, gw, None if direct else gb
+
+
 class _LinearFn(torch.autograd.Function):
     """`relu=True`: the layer AND the ReLU that follows it (round 2): hipBLASLt's epilogue applies it (`torch._addmm_activation`:
     bit-identical to addmm + relu, 36 -> 40 us instead of 52 for 16384 x 934 x 1024), the backward masks the incoming gradient with the
     saved output before the weight / bias / input gradients are formed."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu=False):
+    def forward(ctx, x, weight, bias, relu):
         with torch.autocast("cuda", enabled=False):
             xb = x.to(torch.bfloat16)
-            # inside FlatGradBucket.shadow_scope() the optimizer kernel keeps a bf16 copy of every parameter up to date
-            live = getattr(weight, "_shadow_live", None)
-            if live is not None and live[0]:
-                wb, bb = weight._bf16_shadow, bias._bf16_shadow
-            else:
-                wb, bb = weight.to(torch.bfloat16), bias.to(torch.bfloat16)
+            wb, bb = _bf16_params(weight, bias)
             wb, xb = _match_cols(wb, xb)
             y = torch._addmm_activation(bb, xb, wb.t()) if relu else torch.addmm(bb, xb, wb.t())
         if relu:
@@ -268,42 +300,11 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        if ctx.relu:
-            xb, wb, y = ctx.saved_tensors
-            weight, bias = ctx.params
-            gy = gy.contiguous()
-            if ctx.needs_input_grad[2] and gy.dtype == torch.bfloat16:
-                # ReLU mask and bias gradient in ONE pass over the output gradient (phc_colsum_relu_bf16)
-                direct = _first_write(bias)
-                gm, gb = colsum_relu_bf16(gy, y, out=bias.grad if direct else None)
-                gx, gw, _ = _LinearFn._grads(ctx, gm, xb, wb, skip_bias=True)
-                return gx, gw, (None if direct else gb), None
-            gy = torch.ops.aten.threshold_backward(gy, y, 0.0)
-            gx, gw, gb = _LinearFn._grads(ctx, gy, xb, wb)
-            return gx, gw, gb, None
-        xb, wb = ctx.saved_tensors
-        return _LinearFn._grads(ctx, gy.contiguous(), xb, wb) + ((None,) if len(ctx.needs_input_grad) > 3 else ())
-
-    @staticmethod
-    def _grads(ctx, gy, xb, wb, skip_bias=False):
+        xb, wb = ctx.saved_tensors[:2]
+        y = ctx.saved_tensors[2] if ctx.relu else None
         weight, bias = ctx.params
-        gx = (gy @ wb).to(ctx.x_dtype) if ctx.needs_input_grad[0] else None
-        gw = gb = None
-        if ctx.needs_input_grad[1]:
-            gw = _wgrad_into(weight, gy, xb)
-        if ctx.needs_input_grad[2] and not skip_bias:
-            if _first_write(bias):
-                colsum_bf16(gy, out=bias.grad)
-            else:
-                gb = colsum_bf16(gy)
-        return gx, gw, gb
-
-
-def _bf16_params(weight, bias):
-    live = getattr(weight, "_shadow_live", None)
-    if live is not None and live[0]:
-        return weight._bf16_shadow, bias._bf16_shadow
-    return weight.to(torch.bfloat16), bias.to(torch.bfloat16)
+        _, gx, gw, gb = _linear_grads(gy, xb, wb, weight, bias, y, ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.x_dtype)
+        return gx, gw, gb, None
 
 
 _INPUT_GRAD_ONLY = [False, 0]   # [active, first row of the cotangent's non-zero block]
@@ -354,13 +355,6 @@ def _placeholder(like):
     return _placeholders[key].detach()
 
 
-def _relu_mask(g, y, out=None):
-    """g where y > 0 else 0 (the ReLU's backward), optionally into `out`."""
-    if out is None:
-        return torch.ops.aten.threshold_backward(g, y, 0.0)
-    return torch.ops.aten.threshold_backward.grad_input(g, y, 0.0, grad_input=out)
-
-
 class _LinearDDFn(torch.autograd.Function):
     """The same layer for the discriminator, whose gradient penalty differentiates the backward pass (create_graph=True): the
     backward is itself an autograd node (`_LinearDDBwdFn`) with an explicit second-order rule, so both the first- and the
@@ -369,7 +363,7 @@ class _LinearDDFn(torch.autograd.Function):
     node (piecewise constant: the second-order rule only gains `d gy = m * (...)` and uses the masked gradient everywhere else)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu=False):
+    def forward(ctx, x, weight, bias, relu):
         wb, bb = _bf16_params(weight, bias)
         wb, xb = _match_cols(wb, x.to(torch.bfloat16))
         y = torch._addmm_activation(bb, xb, wb.t()) if relu else torch.addmm(bb, xb, wb.t())
@@ -390,8 +384,8 @@ class _LinearDDFn(torch.autograd.Function):
         only_x, r0 = _INPUT_GRAD_ONLY
         need_gx = ctx.needs_input_grad[0] and not (_PARAM_GRAD_ONLY[0] and ctx.x_is_net_input)
         gx, gw, gb = _LinearDDBwdFn.apply(gy, x, weight, bias, need_gx, only_x, y, r0 if only_x else 0)
-        out = (gx if need_gx else None, None if (only_x or gw.dim() != 2) else gw, None if (only_x or gb.dim() != 1) else gb)   # (0-dim gw / gb: written in place)
-        return out + ((None,) if len(ctx.needs_input_grad) > 3 else ())
+        # (0-dim gw / gb: written in place)
+        return gx if need_gx else None, None if (only_x or gw.dim() != 2) else gw, None if (only_x or gb.dim() != 1) else gb, None
 
 
 class _LinearDDBwdFn(torch.autograd.Function):
@@ -423,29 +417,12 @@ class _LinearDDBwdFn(torch.autograd.Function):
             ctx.mark_non_differentiable(pw, pb)
             return gx, pw, pb
         _, xb = _match_cols(wb, x.to(torch.bfloat16))
-        gb = None
         # the bias receives ONE contribution per step (the penalty path asks for no parameter gradient, the second-order rule has no bias term): when it is
         # the first write into a bucket gradient the column sums are stored there directly -- no tensor for autograd to add (one launch per layer, round 5)
-        direct_b = (gy.dtype == torch.bfloat16 and bias.grad is not None and bias.grad.is_contiguous() and not os.environ.get("PHC_NO_DIRECT_DD_BIAS")
-                    and _first_write(bias))
-        if y is not None:
-            if gy.dtype != torch.bfloat16:
-                gy = _relu_mask(gy, y)
-            else:
-                gy, gb = colsum_relu_bf16(gy, y, out=bias.grad if direct_b else None)          # mask + bias gradient in one pass
-            ctx.save_for_backward(gy, wb, xb, y)
-        else:
-            ctx.save_for_backward(gy, wb, xb)
-        gx = _pad_like((gy @ wb).to(x.dtype), x) if need_gx else _placeholder(gy)
-        gw = _wgrad_into(weight, gy, xb)
-        if gw is None:        # stored / added in place
-            gw = _placeholder(gy)
-            ctx.mark_non_differentiable(gw)
-        if gb is None:
-            gb = colsum_bf16(gy, out=bias.grad if direct_b else None)
-        if direct_b:
-            gb = _placeholder(gy)
-            ctx.mark_non_differentiable(gb)
+        gz, gx, gw, gb = _linear_grads(gy, xb, wb, weight, bias, y, need_gx, True, x.dtype, pad_like=x)
+        ctx.save_for_backward(gz, wb, xb, *([y] if y is not None else []))
+        gx, gw, gb = (_placeholder(gz) if g is None else g for g in (gx, gw, gb))
+        ctx.mark_non_differentiable(*(g for g in (gw, gb) if g.dim() == 0))      # (the placeholders of gradients stored / added in place)
         return gx, gw, gb
 
     @staticmethod
@@ -484,22 +461,33 @@ class _LinearDDBwdFn(torch.autograd.Function):
         return d_gy, d_x, d_w, None, None, None, None, None
 
 
-def _device_training_pass(mod, x):
-    return (x.is_cuda and x.dim() == 2 and torch.is_grad_enabled() and mod.weight.requires_grad and mod.bias is not None
-            and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.is_contiguous())
+class _DeviceLinear(nn.Linear):
+    """What FastLinear, FastLinearDD and FastLinear1DD share: when their own autograd nodes run, and the plain nn.Linear otherwise."""
+
+    def _device_pass(self, x):
+        """A training pass under bf16 autocast on the device: the layer's own autograd node runs."""
+        return (x.is_cuda and x.dim() == 2 and torch.is_grad_enabled() and self.weight.requires_grad and self.bias is not None
+                and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.is_contiguous())
+
+    def _unpad(self, x):
+        """The layer input without the zero pad columns a K-padded input carries (see _match_cols)."""
+        return x[..., :self.in_features] if x.shape[-1] > self.in_features else x
+
+    def _fallback(self, x):
+        return nn.functional.linear(self._unpad(x), self.weight, self.bias)
 
 
-class FastLinearDD(nn.Linear):
+class FastLinearDD(_DeviceLinear):
     """nn.Linear for layers that are differentiated twice (the discriminator MLP): see _LinearDDFn."""
     fuse_relu = False
     _fused_now = False
 
     def forward(self, x):
         self._fused_now = False
-        if _device_training_pass(self, x):
+        if self._device_pass(x):
             self._fused_now = self.fuse_relu
-            return _LinearDDFn.apply(x, self.weight, self.bias, True) if self.fuse_relu else _LinearDDFn.apply(x, self.weight, self.bias)
-        return nn.functional.linear(x[..., :self.in_features] if x.shape[-1] > self.in_features else x, self.weight, self.bias)   # (x may be K-padded)
+            return _LinearDDFn.apply(x, self.weight, self.bias, self.fuse_relu)
+        return self._fallback(x)
 
 
 def _linear1_forward(xb, wb, bb):
@@ -508,6 +496,27 @@ def _linear1_forward(xb, wb, bb):
     y = torch.empty((rows, 1), dtype=torch.bfloat16, device=xb.device)
     L.check(lib.phc_linear1_forward(xb.data_ptr(), wb.data_ptr(), bb.data_ptr(), rows, cols, y.data_ptr(), _stream(xb.device)), "phc_linear1_forward")
     return y
+
+
+def _linear1_backward(xb, wb, gy, gx=None, out=None):
+    """`phc_linear1_backward` of a one-output layer: gx = gy w into `gx` (bf16 [rows, cols]; skipped when None) and [gw | gb] = gy^T [xb | 1]
+    (fp32 [cols + 1]) into `out` -- a bucket gradient whose weight and bias are adjacent -- or a new tensor -> that [cols + 1] result.  Inside
+    `deferred_colsums()` an `out` only gets the first stage: the result is finished with the pass's other column sums."""
+    lib = L.load()
+    rows, cols = xb.shape
+    if _defer(out):
+        ws = _workspace(("lin1", out.data_ptr()), lib.phc_linear1_workspace(rows, cols), xb.device, torch.float32)
+        dst = None
+    else:
+        if out is None:
+            out = torch.empty(cols + 1, dtype=torch.float32, device=xb.device)
+        ws = _workspace("lin1", lib.phc_linear1_workspace(rows, cols), xb.device, torch.float32)
+        dst = out.data_ptr()
+    L.check(lib.phc_linear1_backward(xb.data_ptr(), wb.data_ptr(), gy.data_ptr(), rows, cols, None if gx is None else gx.data_ptr(), dst, ws.data_ptr(),
+                                     _stream(xb.device)), "phc_linear1_backward")
+    if dst is None:
+        _pend(ws, out, lib.phc_linear1_chunks(rows), cols + 1)
+    return out
 
 
 class _Linear1Fn(torch.autograd.Function):
@@ -525,8 +534,7 @@ class _Linear1Fn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         xb, wb = ctx.saved_tensors
-        lib = L.load()
-        rows, cols = xb.shape
+        cols = xb.shape[1]
         gy = gy.contiguous()
         gx = torch.empty_like(xb) if ctx.needs_input_grad[0] else None
         weight, bias = ctx.params
@@ -538,17 +546,7 @@ class _Linear1Fn(torch.autograd.Function):
             weight._grad_gen = bias._grad_gen = b.gen
         elif _pending and weight.grad is not None and weight.grad.data_ptr() in _pending_dst:
             flush_colsums(weight.grad.device)   # (a second application of the layer in one pass: the first one's pending STORE lands before this one is added)
-        gwb = None if direct else torch.empty(cols + 1, dtype=torch.float32, device=xb.device)
-        if direct and _defer(weight.grad):   # first stage only: the [cols + 1] result is finished with the pass's other column sums
-            ws = _workspace(("lin1", weight.grad.data_ptr()), lib.phc_linear1_workspace(rows, cols), xb.device, torch.float32)
-            L.check(lib.phc_linear1_backward(xb.data_ptr(), wb.data_ptr(), gy.data_ptr(), rows, cols, None if gx is None else gx.data_ptr(), None, ws.data_ptr(),
-                                             _stream(xb.device)), "phc_linear1_backward")
-            _pend(ws, weight.grad, lib.phc_linear1_chunks(rows), cols + 1)
-            gx = gx.to(ctx.x_dtype) if gx is not None else None
-            return gx, None, None
-        ws = _workspace("lin1", lib.phc_linear1_workspace(rows, cols), xb.device, torch.float32)
-        L.check(lib.phc_linear1_backward(xb.data_ptr(), wb.data_ptr(), gy.data_ptr(), rows, cols, None if gx is None else gx.data_ptr(),
-                                         weight.grad.data_ptr() if direct else gwb.data_ptr(), ws.data_ptr(), _stream(xb.device)), "phc_linear1_backward")
+        gwb = _linear1_backward(xb, wb, gy, gx, out=weight.grad if direct else None)
         gx = gx.to(ctx.x_dtype) if gx is not None else None
         return (gx, None, None) if direct else (gx, gwb[:cols].view(1, cols), gwb[cols:])
 
@@ -577,7 +575,6 @@ class _Linear1DDBwdFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gy, x, weight, bias, only_x, r0=0):
-        lib = L.load()
         gy = gy.to(torch.bfloat16).contiguous()
         wb, _ = _bf16_params(weight, bias)
         rows, cols = x.shape
@@ -594,10 +591,7 @@ class _Linear1DDBwdFn(torch.autograd.Function):
         ctx.save_for_backward(gy, wb)
         xb = x.to(torch.bfloat16)
         gx = torch.empty_like(xb)
-        gwb = torch.empty(cols + 1, dtype=torch.float32, device=x.device)
-        ws = _workspace("lin1", lib.phc_linear1_workspace(rows, cols), x.device, torch.float32)
-        L.check(lib.phc_linear1_backward(xb.data_ptr(), wb.data_ptr(), gy.data_ptr(), rows, cols, gx.data_ptr(), gwb.data_ptr(), ws.data_ptr(),
-                                         _stream(x.device)), "phc_linear1_backward")
+        gwb = _linear1_backward(xb, wb, gy, gx)
         return gx.to(x.dtype), gwb[:cols].view(1, cols), gwb[cols:]
 
     @staticmethod
@@ -607,14 +601,10 @@ class _Linear1DDBwdFn(torch.autograd.Function):
             raise NotImplementedError("second-order rule through the logit layer's weight / bias gradient")
         if ggx is None:
             return (None,) * 6
-        lib = L.load()
         gy, wb = ctx.saved_tensors       # (only_x: the row block [r0, n))
         g = ggx[ctx.r0:].to(torch.bfloat16).contiguous()
-        m, cols = g.shape
-        gwb = torch.empty(cols + 1, dtype=torch.float32, device=g.device)
-        ws = _workspace("lin1", lib.phc_linear1_workspace(m, cols), g.device, torch.float32)
-        L.check(lib.phc_linear1_backward(g.data_ptr(), wb.data_ptr(), gy.data_ptr(), m, cols, None, gwb.data_ptr(), ws.data_ptr(), _stream(g.device)),
-                "phc_linear1_backward")
+        cols = g.shape[1]
+        gwb = _linear1_backward(g, wb, gy)
         d_gy = None
         if ctx.needs_input_grad[0]:
             d_gy = torch.zeros((ctx.rows, 1), dtype=torch.bfloat16, device=g.device)
@@ -622,13 +612,13 @@ class _Linear1DDBwdFn(torch.autograd.Function):
         return d_gy, None, gwb[:cols].view(1, cols), None, None, None
 
 
-class FastLinear1DD(nn.Linear):
+class FastLinear1DD(_DeviceLinear):
     """nn.Linear(K, 1) that is differentiated twice (the discriminator's `_disc_logits`): see _Linear1DDFn."""
 
     def forward(self, x):
-        if self.out_features == 1 and _device_training_pass(self, x) and x.dtype == torch.bfloat16:
+        if self.out_features == 1 and self._device_pass(x) and x.dtype == torch.bfloat16:
             return _Linear1DDFn.apply(x, self.weight, self.bias)
-        return nn.functional.linear(x[..., :self.in_features] if x.shape[-1] > self.in_features else x, self.weight, self.bias)   # (x may be K-padded)
+        return self._fallback(x)
 
 
 # ---- split-bf16 layers (round 6, `+learning.params.config.actor_precision=split_bf16`) --------------------------------------------------------------------------
@@ -710,7 +700,7 @@ class _SplitLinearFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
-class FastLinear(nn.Linear):
+class FastLinear(_DeviceLinear):
     fuse_relu = False      # set by network.build_mlp when a ReLU follows: the device passes apply it in the GEMM epilogue
     _fused_now = False     # did the last forward() apply it?  (read by the FusedReLU module that follows in the nn.Sequential)
     split_precision = False   # IMAmpAgent sets it on the actor's layers for `actor_precision=split_bf16`: fp32 activations in, fp32 out, three bf16 GEMMs per product
@@ -719,31 +709,29 @@ class FastLinear(nn.Linear):
         self._fused_now = False
         if self.split_precision and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
             self._fused_now = self.fuse_relu
+            x = self._unpad(x)
             if torch.is_grad_enabled() and self.weight.requires_grad:
-                return _SplitLinearFn.apply(x[:, :self.in_features] if x.shape[1] > self.in_features else x, self.weight, self.bias, self.fuse_relu)
+                return _SplitLinearFn.apply(x, self.weight, self.bias, self.fuse_relu)
             with torch.autocast("cuda", enabled=False):
-                return _split_forward(x[:, :self.in_features] if x.shape[1] > self.in_features else x, self.weight.detach(), self.bias.detach().float().contiguous(), self.fuse_relu)[0]
-        if self.out_features == 1 and x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and x.is_contiguous() and self.bias is not None:
-            if _device_training_pass(self, x):
+                return _split_forward(x, self.weight.detach(), self.bias.detach().float().contiguous(), self.fuse_relu)[0]
+        if self._device_pass(x):
+            if self.out_features == 1 and x.dtype == torch.bfloat16:
                 return _Linear1Fn.apply(x, self.weight, self.bias)
-            live = getattr(self.weight, "_shadow_live", None)
-            if not torch.is_grad_enabled() and live is not None and live[0]:
-                return _linear1_forward(x, self.weight._bf16_shadow, self.bias._bf16_shadow)
-        if (x.is_cuda and x.dim() == 2 and torch.is_grad_enabled() and self.weight.requires_grad and self.bias is not None
-                and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.is_contiguous()):
             self._fused_now = self.fuse_relu
-            return _LinearFn.apply(x, self.weight, self.bias, True) if self.fuse_relu else _LinearFn.apply(x, self.weight, self.bias)
-        live = getattr(self.weight, "_shadow_live", None)
-        if live is not None and live[0] and x.is_cuda and x.dtype == torch.bfloat16 and not torch.is_grad_enabled() and self.bias is not None:
+            return _LinearFn.apply(x, self.weight, self.bias, self.fuse_relu)
+        shadow = _bf16_params(self.weight, self.bias, cast=False) if self.bias is not None else None
+        if shadow is not None and x.is_cuda and x.dtype == torch.bfloat16 and not torch.is_grad_enabled():
             # rollout inference inside FlatGradBucket.shadow_scope(): the bf16 parameter copies are current, no per-call casts
-            wb = self.weight._bf16_shadow
+            wb, bb = shadow
             if x.dim() == 2:
+                if self.out_features == 1 and x.is_contiguous():
+                    return _linear1_forward(x, wb, bb)
                 wb, x = _match_cols(wb, x)
-            if self.fuse_relu and x.dim() == 2:
-                self._fused_now = True
-                return torch._addmm_activation(self.bias._bf16_shadow, x, wb.t())
-            return nn.functional.linear(x, wb, self.bias._bf16_shadow)
-        return nn.functional.linear(x[..., :self.in_features] if x.shape[-1] > self.in_features else x, self.weight, self.bias)   # (x may be K-padded)
+                if self.fuse_relu:
+                    self._fused_now = True
+                    return torch._addmm_activation(bb, x, wb.t())
+            return nn.functional.linear(x, wb, bb)
+        return self._fallback(x)
 
 
 class FusedReLU(nn.ReLU):

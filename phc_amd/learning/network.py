@@ -37,7 +37,7 @@ def build_mlp(input_size, units, activation, linear=nn.Linear):
         lin = linear(n, u)
         if not layers and isinstance(lin, (FastLinear, FastLinearDD)):
             lin.weight._pad_cols = pad_cols(n)   # first layer: store the weight K-padded on the device (FlatGradBucket)
-        if activation == "relu" and isinstance(lin, (FastLinear, FastLinearDD)) and not os.environ.get("PHC_NO_RELU_FUSION"):   # the ReLU rides in the GEMM epilogue of the device passes
+        if activation == "relu" and isinstance(lin, (FastLinear, FastLinearDD)):   # the ReLU rides in the GEMM epilogue of the device passes
             lin.fuse_relu = True
             layers += [lin, FusedReLU(lin)]
         else:
