@@ -432,6 +432,25 @@ int32_t phc_sum_slabs_bf16(const void* part, int32_t slabs, int64_t n, float* ou
 int32_t phc_split3_bf16(const float* x, int64_t ld_in, const float* gate, int64_t ld_gate, int64_t rows, int32_t cols, int64_t rows_pad, int32_t cols_pad,
                         const float* extra, int32_t extra_mode, void* out, int64_t row_stride, int64_t chunk_stride, int32_t order, void* stream);
 
+/* Native weight gradient of a bf16 linear layer (csrc/phc_gemm.hip; opt-in, `+learning.params.config.wgrad=native`; additions to ABI 37, which stays 37).
+ * For gy, y bf16 [rows, n] (contiguous) and x bf16 [rows, k] whose rows are `ld_x` elements apart (ld_x >= k: K-padded inputs):
+ *   gz[r, j]  = y == NULL ? gy[r, j] : (y[r, j] > 0 ? gy[r, j] : 0)        bf16 [rows, n], a select (autograd's ThresholdBackward)
+ *   gw[j, c] (=|+=) sum_r gz[r, j] * x[r, c]                                fp32, rows `ld_gw` floats apart (ld_gw >= k)   (AddmmBackward: gz^T x)
+ *   gb[j]    (=|+=) sum_r gz[r, j]                                          fp32 [n]
+ * on the matrix cores with fp32 accumulation; the rows are cut into phc_wgrad_bf16_slices(rows, n, k) slices (a function of the shape alone) whose fp32
+ * partial tiles are added in slice order inside the same launch, so the result is bit-identical from call to call.  `accumulate` / `gb_accumulate`
+ * != 0 add to gw / gb instead of storing.
+ * May be NULL: y (no mask), gz (not written), gb (not computed).  gz may not alias gy or y.
+ * Alignment: bf16 pointers 2 bytes, gw / gb 4 bytes, workspace 16 bytes.  16-byte accesses are used for gy / y / gz when all three are 16-byte aligned and n
+ * is a multiple of 8, and for x when it is 16-byte aligned and ld_x and k are multiples of 8; element accesses otherwise (every rows, n, k >= 1 is served).
+ * workspace: phc_wgrad_bf16_workspace(rows, n, k) bytes of device memory holding one arrival counter per 128 x 128 output tile (zeroed on `stream` by every
+ * call, by a kernel node -- a captured memset node does not replay reliably on this stack --: nothing to initialise), the slices' fp32 tile slabs and their bias partial sums.  It must not be shared by launches that may run concurrently
+ * (one per stream).  Null / non-positive arguments return PHC_EINVAL before the device is touched. */
+int32_t phc_wgrad_bf16_slices(int64_t rows, int32_t n, int32_t k);
+int64_t phc_wgrad_bf16_workspace(int64_t rows, int32_t n, int32_t k);
+int32_t phc_wgrad_bf16(const void* gy, const void* y, const void* x, int64_t ld_x, int64_t rows, int32_t n, int32_t k, float* gw, int64_t ld_gw,
+                       int32_t accumulate, void* gz, float* gb, int32_t gb_accumulate, void* workspace, void* stream);
+
 /* Discriminator loss pieces (phc/learning/amp_agent.py:732-808 `_disc_loss`).
  * phc_disc_bce: logits [n_agent + n_demo] (agent and replay rows first, demo rows last; bf16 or fp32):
  *   stats[0] = scale * 0.5 (BCEWithLogits(agent, 0) + BCEWithLogits(demo, 1)), stats[1] = mean(agent < 0), stats[2] = mean(demo > 0),

@@ -109,6 +109,9 @@ _SIGNATURES = {
     "phc_colsum_bf16": ([c_p, c_i64, c_i32, c_p, c_p, c_p], c_i32),
     "phc_colsum_relu_bf16": ([c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p], c_i32),
     "phc_sum_slabs_bf16": ([c_p, c_i32, c_i64, c_p, c_i32, c_p], c_i32),
+    "phc_wgrad_bf16_slices": ([c_i64, c_i32, c_i32], c_i32),
+    "phc_wgrad_bf16_workspace": ([c_i64, c_i32, c_i32], c_i64),
+    "phc_wgrad_bf16": ([c_p, c_p, c_p, c_i64, c_i64, c_i32, c_i32, c_p, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_p], c_i32),
     "phc_split3_bf16": ([c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_i64, c_i32, c_p, c_i32, c_p, c_i64, c_i64, c_i32, c_p], c_i32),
     "phc_colsum_chunks": ([c_i64], c_i32),
     "phc_linear1_chunks": ([c_i64], c_i32),

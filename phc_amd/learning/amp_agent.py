@@ -325,6 +325,11 @@ class IMAmpAgent:
                 if isinstance(m, FastLinear):
                     m.split_precision = True
                     m.weight._pad_cols = 0      # (the split layers read the fp32 master weights: no K-padded bf16 copy)
+        # `wgrad=native`: the weight / bias gradients of the bf16 device layers by the project's own matrix-core kernel (fast_ops.set_wgrad, csrc/phc_gemm.hip)
+        # instead of the library's batched GEMM between two reduction passes; opt-in, `library` is the default.  Inert off the device.
+        from .fast_ops import set_wgrad
+        self._wgrad = str(c.get("wgrad", "library"))
+        set_wgrad(self.model, self._wgrad)
         self.grads = FlatGradBucket(self.model.parameters())
         # K-padded first layers: width of the padded input buffers the normalisers write (0: no padding; see FlatGradBucket)
         padded_k = {p.shape[1]: p._padded.shape[1] for p in self.grads.params if getattr(p, "_padded", None) is not None}

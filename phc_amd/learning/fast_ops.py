@@ -5,6 +5,8 @@
   as a batched GEMM over 8 row chunks + fp32 sum (the library's pick for a 16 384-long reduction is a 240-workgroup kernel without
   split-K: 105-115 us vs 44-68 us, scripts/probes/gemm_probe2.py); bias gradient by `phc_colsum_bf16`; one-output layers (the value head)
   by `phc_linear1_*`.  Used for actor, critic, PNN columns.
+  With `+learning.params.config.wgrad=native` (`set_wgrad`) mask, weight gradient and bias gradient are ONE launch of the project's own MFMA kernel
+  (`phc_wgrad_bf16`, csrc/phc_gemm.hip), fp32 up to the gradient bucket.
 * `FastLinearDD` -- the same, differentiable twice, for the discriminator MLP whose gradient penalty differentiates the backward pass.
 * `ppo_loss`, `disc_bce`, `weighted_sumsq` -- the loss terms with their gradients as kernels (unit-weight convention, see `_PPOLossFn`).
 * `policy_sample` -- the rollout's sampling / neglogp / value un-normalisation in one kernel.
@@ -257,11 +259,77 @@ def _relu_mask(g, y, out=None):
     return torch.ops.aten.threshold_backward.grad_input(g, y, 0.0, grad_input=out)
 
 
-def _linear_grads(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like=None):
+WGRAD_MODES = ("library", "native")
+
+
+def set_wgrad(module, mode):
+    """`+learning.params.config.wgrad`: which kernels form the weight / bias gradients of the bf16 device layers under `module` -- `library`
+    (the default: phc_colsum_relu_bf16 / phc_colsum_bf16, a batched library GEMM over SPLIT_K row chunks, phc_sum_slabs_bf16) or `native` (one
+    phc_wgrad_bf16 launch: mask, weight gradient, bias gradient, fp32 from the matrix cores' accumulator to the gradient bucket).  The switch is a
+    tag on the weight; it only acts where `_linear_grads` runs (training under bf16 autocast on the device, parameters in a FlatGradBucket)."""
+    if mode not in WGRAD_MODES:
+        raise ValueError(f"learning.params.config.wgrad must be library or native, not {mode!r}")
+    for m in module.modules():
+        if isinstance(m, _DeviceLinear):
+            m.weight._wgrad_native = mode == "native"
+
+
+def wgrad_native(gy, y, xb, gw, accumulate=False, gz=None, gb=None, gb_accumulate=False):
+    """One phc_wgrad_bf16 launch: gy, y (or None) bf16 [rows, n] contiguous, xb bf16 [rows, k] with unit column stride -> gw fp32 [n, k] (rows
+    gw.stride(0) apart) stored or added to; optionally gz = gy masked by y > 0 (bf16 [rows, n]) and gb fp32 [n] stored or added to."""
+    lib = L.load()
+    rows, n = gy.shape
+    k = xb.shape[1]
+    # one workspace per STREAM (and lane): it holds the launch's arrival counters and slabs, so two launches that may overlap must never share it -- a lane
+    # name alone is not enough once a finished agent's stream handle is reused by another agent's stream
+    stream = _stream(gy.device)
+    ws = _workspace(("wgrad", stream), lib.phc_wgrad_bf16_workspace(rows, n, k), gy.device, torch.uint8)
+    L.check(lib.phc_wgrad_bf16(gy.data_ptr(), None if y is None else y.data_ptr(), xb.data_ptr(), xb.stride(0) if rows > 1 else max(xb.stride(0), k), rows, n, k,
+                               gw.data_ptr(), gw.stride(0) if n > 1 else max(gw.stride(0), k), int(accumulate), None if gz is None else gz.data_ptr(),
+                               None if gb is None else gb.data_ptr(), int(gb_accumulate), ws.data_ptr(), stream), "phc_wgrad_bf16")
+    return gw
+
+
+def _native_dest(weight, gy, xb, y):
+    """Where the native kernel writes this layer's weight gradient (the parameter's gradient or its K-padded storage), or None when the layer
+    keeps the library path: switch off, not a bf16 device pass, parameter outside a FlatGradBucket, destination not contiguous."""
+    if not getattr(weight, "_wgrad_native", False) or not gy.is_cuda or gy.dtype != torch.bfloat16 or xb.dtype != torch.bfloat16:
+        return None
+    if getattr(weight, "_bucket", None) is None or weight.grad is None or gy.dim() != 2 or gy.shape[0] < 1:
+        return None
+    out = _grad_out(weight, xb.shape[1])
+    if out.shape[1] != xb.shape[1] or not out.is_contiguous() or out.dtype != torch.float32 or xb.stride(1) != 1:
+        return None
+    if y is not None and (not y.is_contiguous() or y.dtype != torch.bfloat16):
+        return None
+    return out
+
+
+def _linear_grads_native(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like, keep_gz, dest):
+    """_linear_grads with ONE phc_wgrad_bf16 launch in place of the column sums, the batched GEMM and the slab sum; the input gradient stays the
+    library's GEMM on the same gz and runs after it."""
+    gz = gy if y is None else (torch.empty_like(gy) if (need_gx or keep_gz) else None)
+    gb = gb_acc = direct = None
+    if need_gb:
+        direct = getattr(bias, "_bucket", None) is not None and bias.grad is not None and bias.grad.is_contiguous() and bias.grad.dtype == torch.float32
+        if direct:
+            gb, gb_acc = bias.grad, not _first_write(bias)     # (never a deferred column-sum job: the kernel finishes the sum itself)
+        else:
+            gb, gb_acc = torch.empty(gy.shape[1], dtype=torch.float32, device=gy.device), False
+    wgrad_native(gy, y, xb, dest, accumulate=not _first_write(weight), gz=None if y is None else gz, gb=gb, gb_accumulate=gb_acc)
+    gx = _pad_like((gz @ wb).to(x_dtype), pad_like) if need_gx else None
+    return gz, gx, None, None if direct else gb
+
+
+def _linear_grads(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like=None, keep_gz=False):
     """First-order backward of a bf16 layer y = x W^T + b (and of the ReLU behind it when its output `y` is given) -> (gz, gx, gw, gb):
     gz = gy masked by y > 0, gx = gz W (brought to the width of `pad_like` when given, see _pad_like), gw = gz^T xb, gb = 1^T gz;
-    gw / gb are None when they were stored or added in the parameter's bucket gradient (_wgrad_into, _first_write)."""
+    gw / gb are None when they were stored or added in the parameter's bucket gradient (_wgrad_into, _first_write).
+    `keep_gz`: the caller reads gz (with `wgrad=native` it is only materialised for that or for gx)."""
     gy = gy.contiguous()
+    dest = _native_dest(weight, gy, xb, y)
+    if dest is not None:
+        return _linear_grads_native(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like, keep_gz, dest)
     gb = direct = None       # direct: the bias gradient goes straight into the bucket (None: not decided yet)
     if y is not None:
         if need_gb and gy.dtype == torch.bfloat16:
@@ -419,7 +487,7 @@ class _LinearDDBwdFn(torch.autograd.Function):
         _, xb = _match_cols(wb, x.to(torch.bfloat16))
         # the bias receives ONE contribution per step (the penalty path asks for no parameter gradient, the second-order rule has no bias term): when it is
         # the first write into a bucket gradient the column sums are stored there directly -- no tensor for autograd to add (one launch per layer, round 5)
-        gz, gx, gw, gb = _linear_grads(gy, xb, wb, weight, bias, y, need_gx, True, x.dtype, pad_like=x)
+        gz, gx, gw, gb = _linear_grads(gy, xb, wb, weight, bias, y, need_gx, True, x.dtype, pad_like=x, keep_gz=True)
         ctx.save_for_backward(gz, wb, xb, *([y] if y is not None else []))
         gx, gw, gb = (_placeholder(gz) if g is None else g for g in (gx, gw, gb))
         ctx.mark_non_differentiable(*(g for g in (gw, gb) if g.dim() == 0))      # (the placeholders of gradients stored / added in place)
