@@ -527,6 +527,58 @@ int32_t phc_ppo_loss(const void* mu, const void* value, int32_t is_bf16, const f
                      const int64_t* row_index, int64_t batch, int32_t num_actions, const phc_ppo_params_t* prm, void* grad_mu, void* grad_value, float* stats,
                      double* workspace, void* stream);
 
+/* Offscreen renderer (csrc/phc_render.hip; additions to ABI 37, which stays 37).  Replaces the reference's camera sensor + video writer of the
+ * player (phc/env/tasks/base_task.py:176-195,405-437; humanoid.py:1715-1743 `_init_camera` / `_update_camera`; humanoid_im.py:597-619 markers):
+ * a ray caster over the articulation's collision capsules, off the training path.  Each view is a pinhole camera on ONE env; the scene of a view:
+ *   * every collision capsule s < num_capsules of the env's shape block (a box is drawn as its capsule stand-in), posed by the owner body's
+ *     rigid_body_state row (pos3, xyzw quaternion);
+ *   * the ground plane z = 0 with a 1 m two-tone checker: ground_color[(floor(x) + floor(y)) & 1];
+ *   * optional marker spheres (radius marker_radius) at markers[env, m];
+ *   * sky_color where a ray hits nothing.
+ * Shading of a hit with unit normal n, base colour C (palette[owner % PHC_RENDER_PALETTE] for a capsule, marker_color, the checker tone):
+ *   lit = max(n . light_dir, 0), set to 0 when the shadow ray from (hit + 1e-3 n) toward light_dir enters any capsule or marker at t > 0
+ *   (the ground is not an occluder: a light above the horizon is assumed);
+ *   rgb = C * (ambient + diffuse * lit), each channel stored as u8 floor(min(max(v, 0), 1) * 255 + 0.5); alpha 255.
+ * Ray of pixel (x, y) (row y = 0 at the top): f = |target - eye|^-1 (target - eye), r = |f x up|^-1 (f x up), u = r x f,
+ *   d = unit(f + ((2 (x + 0.5) / W - 1) tan(fov_y / 2) W / H) r + ((1 - 2 (y + 0.5) / H) tan(fov_y / 2)) u).
+ * Outputs: rgba u8 [V, H, W, 4]; depth f32 [V, H, W] (nullable): t of the first hit along the unit ray, +inf on a miss; hit_id i32 [V, H, W]
+ * (nullable): -1 sky, -2 ground, s for capsule s of the env's block, PHC_RENDER_MARKER_ID + m for marker m.  Deterministic (no atomics).
+ * PHC_EINVAL before any device work for: a null required pointer (scene, cameras, rgba, body_state, capsules; markers when num_markers > 0),
+ * views <= 0, width or height <= 0, width * height > PHC_RENDER_MAX_PIXELS, a camera env outside [0, num_envs), num_capsules outside
+ * [1, PHC_RENDER_MAX_SHAPES], num_markers outside [0, PHC_RENDER_MAX_MARKERS], num_bodies outside [1, PHC_MAX_BODIES], num_shape_blocks < 1,
+ * a capsule_stride below 8 num_capsules.  An env_shape entry outside [0, num_shape_blocks) selects block 0; a capsule whose owner is outside
+ * [0, num_bodies) or whose radius is <= 0 is not drawn. */
+#define PHC_RENDER_MAX_PIXELS (1 << 24)   /* width * height of one view */
+#define PHC_RENDER_MAX_SHAPES 128
+#define PHC_RENDER_MAX_MARKERS 128
+#define PHC_RENDER_PALETTE 16
+#define PHC_RENDER_MARKER_ID 1000
+typedef struct {
+    int32_t env;                      /* env whose bodies the view shows */
+    float eye[3], target[3], up[3];   /* world frame, metres */
+    float fov_y;                      /* vertical field of view, radians */
+} phc_camera_t;
+typedef struct {
+    int32_t num_envs, num_bodies;     /* N, NB */
+    const float* body_state;          /* [N, NB, 13] rigid_body_state */
+    const float* capsules;            /* [K, capsule_stride]: capsule s of block k at capsules[k * capsule_stride + 8 s]: a[3], b[3] (owner frame), radius, owner (as a float) */
+    int32_t num_capsules;             /* S (ArticulationModel.shape_capsules(): primary then extra capsules) */
+    int32_t num_shape_blocks;         /* K */
+    int64_t capsule_stride;           /* floats between two blocks, >= 8 S */
+    const int32_t* env_shape;         /* [N] block of each env (phc_sim_state_t.env_shape); nullable = block 0 */
+    const float* markers;             /* [N, M, 3] world positions; nullable when M = 0 */
+    int32_t num_markers;              /* M */
+    float marker_radius;
+    float palette[PHC_RENDER_PALETTE][3];   /* body colours, linear 0..1 */
+    float marker_color[3];
+    float ground_color[2][3];
+    float sky_color[3];
+    float light_dir[3];               /* unit vector toward the light */
+    float ambient, diffuse;
+} phc_render_scene_t;
+int32_t phc_render(const phc_render_scene_t* scene /* host */, const phc_camera_t* cameras /* host, [views] */, int32_t views, int32_t width,
+                   int32_t height, uint8_t* rgba, float* depth, int32_t* hit_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

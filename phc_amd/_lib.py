@@ -87,6 +87,24 @@ class PpoParams(C.Structure):
     _fields_ = [("e_clip", c_f), ("critic_coef", c_f), ("entropy_coef", c_f), ("bounds_loss_coef", c_f), ("clip_value", c_i32)]
 
 
+RENDER_PALETTE = 16          # PHC_RENDER_PALETTE
+RENDER_MARKER_ID = 1000      # PHC_RENDER_MARKER_ID
+RENDER_MAX_PIXELS = 1 << 24  # PHC_RENDER_MAX_PIXELS
+RENDER_MAX_SHAPES = 128      # PHC_RENDER_MAX_SHAPES
+RENDER_MAX_MARKERS = 128     # PHC_RENDER_MAX_MARKERS
+
+
+class Camera(C.Structure):
+    _fields_ = [("env", c_i32), ("eye", c_f * 3), ("target", c_f * 3), ("up", c_f * 3), ("fov_y", c_f)]
+
+
+class RenderScene(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("body_state", c_p), ("capsules", c_p), ("num_capsules", c_i32),
+                ("num_shape_blocks", c_i32), ("capsule_stride", c_i64), ("env_shape", c_p), ("markers", c_p), ("num_markers", c_i32),
+                ("marker_radius", c_f), ("palette", (c_f * 3) * RENDER_PALETTE), ("marker_color", c_f * 3), ("ground_color", (c_f * 3) * 2),
+                ("sky_color", c_f * 3), ("light_dir", c_f * 3), ("ambient", c_f), ("diffuse", c_f)]
+
+
 P = C.POINTER
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
@@ -128,6 +146,7 @@ _SIGNATURES = {
     "phc_adam_clip_step": ([c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_f, c_p, c_p, c_p, c_p, c_p], c_i32),
     "phc_ppo_loss_workspace": ([], c_i64),
     "phc_ppo_loss": ([c_p, c_p, c_i32] + [c_p] * 9 + [c_i64, c_i32, P(PpoParams), c_p, c_p, c_p, c_p, c_p], c_i32),
+    "phc_render": ([P(RenderScene), P(Camera), c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -14,8 +14,9 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #   stepper: see the header of phc_sim.hip (-ffast-math -fno-slp-vectorize: 158 -> 109 us).
 #   learner kernels: bandwidth-bound passes; IEEE division / no contraction so the normalised values equal torch's.
 #   matrix-core kernels (phc_gemm.hip): no contraction either (the fp32 slab and bias sums are plain adds in a fixed order).
+#   renderer (phc_render.hip, off the training path): IEEE fp32 (no fast-math): its error bound assumes correctly rounded sqrt / division.
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
-           "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"]}
+           "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": []}
 HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 

@@ -1118,7 +1118,16 @@ class HumanoidIm:
         L.check(self._lib.phc_refresh_body_state(self._model_struct, self._sim_struct, _stream()), "phc_refresh_body_state")
 
     def render(self, sync_frame_time=False):
-        return
+        """Offscreen recording (base_task.py:405-437 with the camera sensor of :176-195): with `+render.video=<dir>` one frame of the
+        followed env(s) per call, drawn by phc_render (phc_amd/render.py); otherwise nothing, as before.  Reads simulator state only."""
+        rc = self.cfg.get("render", None) or {}
+        if not rc.get("video", None):
+            return
+        if getattr(self, "_recorder", None) is None:
+            from ...render import TaskRecorder
+            self._recorder = TaskRecorder(self, rc)
+        self._recorder.record()
 
     def close(self):
-        return
+        if getattr(self, "_recorder", None) is not None:
+            self._recorder.close()

@@ -55,6 +55,7 @@ def main(argv=None):
                 print({k: (round(v, 4) if isinstance(v, float) else v) for k, v in info.items()}, "failed clips:", len(failed))
         else:
             info = play(agent, task, env, steps=int(cfg.get("games", 300)))
+            task.close()   # (finishes a `+render.video` recording)
             if rank == 0:
                 print(info)
         if dist is not None:
@@ -81,6 +82,7 @@ def play(agent, task, env, steps=300):
     with torch.no_grad():
         for _ in range(steps):
             obs, r, done, info = env.step(agent.preprocess_actions(agent.get_action_values(obs)["mus"]))
+            task.render()   # one frame per env step with `+render.video=DIR` (base_task.py:405-437); a no-op otherwise
             rew_sum += r
             ep_len += 1
             ids = done.nonzero(as_tuple=False).flatten()
