@@ -24,9 +24,13 @@ MI355X-first differences (results-preserving):
   * on the device everything of the update that is not a GEMM runs as HIP kernels (csrc/phc_learn.hip via learning/fast_ops.py,
     DESIGN.md 4.3): observation normalisers incl. the minibatch gather, actor / critic and discriminator losses with their
     gradients, bias and split-K weight gradients of the layers, clip + Adam on the flat parameter, the rollout's sampling step;
-    optionally (`hip_graph`) the forward / backward of a step is replayed from one captured hipGraph.  The torch expressions in
+    optionally (`hip_graph`) a step is replayed from captured hipGraphs (update_graph.py).  The torch expressions in
     this file (`_ppo_loss_torch`, `_disc_loss`, RunningMeanStd's CPU branch) remain the CPU path and the definition those kernels
     are tested against.
+
+`IMAmpAgent` owns the reference's agent surface, the rollout (`play_steps`: eager, segment graphs, whole-step graphs), the dataset and its
+minibatch draw, checkpoints, and ONE definition of the optimizer step: `_fwd_bwd` dispatches to `_device_step` (`_policy_pass` + `_disc_pass`, on
+two streams or one) or to the torch path; `update_graph.CapturedUpdate` captures those same methods.  `__init__` assigns every attribute.
 """
 import copy
 import os
@@ -41,8 +45,10 @@ from torch import nn
 from .. import _lib as L
 from .network import A2CMCPNetwork, A2CNetwork, A2CPNNNetwork, ModelAMPContinuous, policy_kl
 from .replay_buffer import ReplayBuffer
-from .fast_ops import adam_clip_step, deferred_colsums, disc_bce, input_grad_only, param_grad_only, policy_sample, ppo_loss, rows_with_grad, weighted_sumsq
+from .fast_ops import (FastLinear, adam_clip_step, deferred_colsums, disc_bce, input_grad_only, param_grad_only, policy_sample, ppo_loss, register_lane, rows_with_grad,
+                       set_wgrad, weighted_sumsq)
 from .running_mean_std import RunningMeanStd
+from .update_graph import CapturedUpdate
 
 
 def swap_and_flatten01(arr):
@@ -250,15 +256,15 @@ class IMAmpAgent:
         c = params["config"]
         # `force_collectives`: run the gradient all-reduce also in a one-rank process group (tests: RCCL next to the captured update on one GPU)
         self._force_collectives = bool(c.get("force_collectives", False))
+        self._reduces = self.multi_gpu or (self._force_collectives and dist is not None)   # is there a gradient all-reduce between backward and optimizer?
         self.allreduce_timing = None   # bench.py sets a list: (start, end) events of every gradient all-reduce
         self._trace = [] if c.get("trace_minibatches", False) else None
-        self._step_in_epoch = 0
-        # diagnostic (round 6): True = rounds 1-5's behaviour, the envs that finished on the last step of a rollout are reset at step 0 of the next one
-        self._reset_at_rollout_start = bool(c.get("debug_reset_at_rollout_start", False))
+        for k in ("debug_actor_steps", "debug_critic_steps", "debug_disc_steps", "debug_reset_at_rollout_start"):
+            if k in c:   # (the knobs of the round-6 seed study, DESIGN.md section 10: removed with their code, never ignored silently)
+                raise ValueError(f"learning.params.config.{k} is set, but that diagnostic no longer exists (profiles/r06_multi_clip/README.md names the last commit that has it)")
         self.num_collectives = 0       # gradient all-reduces issued so far
         self.config = c
         self.device = self.task.device if hasattr(self.task, "device") else "cpu"
-        self.ppo_device = self.device
         self.bf16 = bf16 and str(self.device).startswith("cuda")
         self.num_actors = vec_env.num_envs
         self.horizon_length = c["horizon_length"]
@@ -320,17 +326,17 @@ class IMAmpAgent:
         if self._actor_split:
             if net_name != "amp" or not self.normalize_input or not self.temp_running_mean:
                 raise NotImplementedError("actor_precision=split_bf16 is built for the plain `amp` network with normalize_input and temp_running_mean")
-            from .fast_ops import FastLinear
             for m in list(net.actor_mlp.modules()) + [net.mu]:
                 if isinstance(m, FastLinear):
                     m.split_precision = True
                     m.weight._pad_cols = 0      # (the split layers read the fp32 master weights: no K-padded bf16 copy)
         # `wgrad=native`: the weight / bias gradients of the bf16 device layers by the project's own matrix-core kernel (fast_ops.set_wgrad, csrc/phc_gemm.hip)
         # instead of the library's batched GEMM between two reduction passes; opt-in, `library` is the default.  Inert off the device.
-        from .fast_ops import set_wgrad
         self._wgrad = str(c.get("wgrad", "library"))
         set_wgrad(self.model, self._wgrad)
         self.grads = FlatGradBucket(self.model.parameters())
+        # the fused discriminator path: its loss runs as kernels (`_disc_loss_fused`) and the whole optimizer step is `_device_step`
+        self._fused_disc = self.grads.flat.is_cuda and self._disc_grad_penalty > 0 and bool(self._normalize_amp_input)
         # K-padded first layers: width of the padded input buffers the normalisers write (0: no padding; see FlatGradBucket)
         padded_k = {p.shape[1]: p._padded.shape[1] for p in self.grads.params if getattr(p, "_padded", None) is not None}
         self._obs_pad_cols = padded_k.get(obs_dim, 0)
@@ -339,7 +345,7 @@ class IMAmpAgent:
         # update the bench line quotes.  Known hazard (scripts/probes/graph_repro2.py): if the caller keeps an autograd-tracked copy of a
         # parameter alive (`w0 = p.clone()` instead of `p.detach().clone()`), that parameter's AccumulateGrad node lives on the stream it was
         # created on; the captured backward then has to hand the gradient to a stream that is not capturing and `hipStreamEndCapture` segfaults on
-        # ROCm 7.2 instead of raising -- `_stale_grad_accumulators()` detects exactly that before capturing and the update falls back to eager
+        # ROCm 7.2 instead of raising -- `update_graph.stale_grad_accumulators()` detects exactly that before capturing and the update falls back to eager
         # launches, as it does when a capture raises or the minibatch is small (< 2048 rows: not launch-bound).
         # the known failure mode of a bad capture on this stack is a crash, not an exception, so the DEFAULT is on only for the (torch, HIP)
         # pairs the -m gpu suite has run the captured update on (VERIFIED_GRAPH_STACKS: tests/test_env_gpu.py::test_update_graph_equals_eager_launches,
@@ -348,16 +354,17 @@ class IMAmpAgent:
         self._use_graph = bool(c["hip_graph"]) if "hip_graph" in c else graph_default_on()
         # The discriminator's share of an optimizer step (three input normalisers, forward, loss terms, the gradient penalty's double backward,
         # backward) shares nothing with actor + critic but the optimizer launches at the end: two chains of ~256-workgroup GEMMs and 5 us
-        # finishing launches.  On the device the discriminator pass runs on its own HIP stream (_fwd_bwd); captured, it is its OWN linear
-        # hipGraph replayed on that stream next to the policy graph (_graph_update).
+        # finishing launches.  On the device the discriminator pass runs on its own HIP stream (_device_step); captured, it is its OWN linear
+        # hipGraph replayed on that stream next to the policy graph (update_graph.CapturedUpdate).
         self._use_branches = bool(c.get("branch_streams", True)) and not os.environ.get("PHC_NO_BRANCH_STREAMS")
         # VERDICT r5 item 6b (UNMEASURED on multi-GPU hardware -- no node was ever available to this project; exercised by two-rank gloo and one-rank RCCL tests): the
         # gradient bucket cut at the policy / discriminator boundary, the discriminator's all-reduce issued on its stream as soon as its pass is done.  Off by default:
         # the shipped path is ONE all-reduce per optimizer step (north star); for `im` the discriminator holds 2.5 M of the 5.8 M gradient elements.
         self._split_allreduce = bool(c.get("split_allreduce", False))
-        self._branches = None
-        self._graph = self._g_data = self._g_idx = self._g_info = None
-        self._graph_failed = False
+        self._branches = None                              # the discriminator's stream, made by the first two-stream step (_branch_streams) ...
+        self._disc_spans = self._policy_spans = None       # ... with the two passes' ranges of the flat gradient
+        self._update = CapturedUpdate(self)                # the optimizer steps of an epoch as replayed hipGraphs (update_graph.py)
+        self._graph_failed = False                         # the FIRST capture raised: eager launches from then on, rollout included
         # one flat fp32 parameter; on the device clip + step are two HIP launches over it (fast_ops.adam_clip_step) and this object
         # only holds the state (checkpoint format unchanged)
         self.optimizer = torch.optim.Adam([self.grads.flat_param], self.last_lr, eps=1e-08, weight_decay=c.get("weight_decay", 0.0))
@@ -378,7 +385,16 @@ class IMAmpAgent:
         self.frame = 0
         self.obs = None
         self.dones = torch.zeros(N, device=dev, dtype=torch.long)
-        self.mean_rewards = []
+        self.dataset = None                # prepare_dataset()
+        # created on first use; a captured graph keeps their addresses, so each is made once and kept
+        self._pad_bufs = {}                # (use, rows, cols) -> zero-padded bf16 input buffer (_pad_buf)
+        self._unit_cot = {}                # (dtype, device) -> the constant cotangent 1 of a loss root (_unit_cotangent)
+        self._raw = None                   # the step's scalars as the fused kernels write them (_raw_buffer)
+        self._ones_key = self._ones = None           # cotangent that selects the demo rows (_demo_row_mask)
+        self._terminated_flags = self._terminated_mask = self._env_actions = None   # rollout scratch (play_steps)
+        self._reward_raw_acc = None        # sum of the rollout's raw reward terms: made by the FIRST rollout, eagerly (whole-step graphs need it to exist)
+        self._roll_graphs, self._roll_pool, self._roll_generation = {}, None, None   # rollout hipGraphs by key, their memory pool, the task's launch generation they hold
+        self._summary_file = self._summary_writer = None      # _log_train_info
 
     # ------------------------------------------------------------------ modes (rl_games set_eval / set_train + amp_agent.py:63-82)
     def _norms(self):
@@ -404,7 +420,7 @@ class IMAmpAgent:
         # bf16 runs: the normaliser writes the bf16 tensor the GEMMs read (the same values autocast's cast would produce)
         dt = torch.bfloat16 if self.bf16 else None
         out = None
-        if obs_batch.is_cuda and self.bf16 and getattr(self, "_obs_pad_cols", 0) > obs_batch.shape[1]:
+        if obs_batch.is_cuda and self.bf16 and self._obs_pad_cols > obs_batch.shape[1]:
             # K-padded first layers (FlatGradBucket): the normaliser writes the left columns of a persistent [rows, Kp] buffer (pad = 0)
             rows = obs_batch.shape[0] if row_index is None else row_index.numel()
             buf = self._pad_buf("obs", rows, self._obs_pad_cols)
@@ -428,11 +444,10 @@ class IMAmpAgent:
 
     def _pad_buf(self, name, rows, cols):
         """Persistent zero-initialised bf16 [rows, cols] buffers (one per use and row count: a captured graph keeps their address)."""
-        bufs = self.__dict__.setdefault("_pad_bufs", {})
         key = (name, rows, cols)
-        if key not in bufs:
-            bufs[key] = torch.zeros((rows, cols), dtype=torch.bfloat16, device=self.device)
-        return bufs[key]
+        if key not in self._pad_bufs:
+            self._pad_bufs[key] = torch.zeros((rows, cols), dtype=torch.bfloat16, device=self.device)
+        return self._pad_bufs[key]
 
     def _preproc_amp_obs(self, amp_obs, row_index=None):
         if not self._normalize_amp_input:
@@ -483,7 +498,7 @@ class IMAmpAgent:
             in_group = self.dist is not None and self.dist.is_initialized()
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            if getattr(self, "_roll_pool", None) is None:   # the rollout graphs replay one after the other and leave their results in the
+            if self._roll_pool is None:   # the rollout graphs replay one after the other and leave their results in the
                 self._roll_pool = torch.cuda.graph_pool_handle()   # persistent experience buffers: their temporaries can share one pool
             with torch.cuda.graph(g, pool=self._roll_pool, capture_error_mode="thread_local" if in_group else "global"):
                 fn()
@@ -494,10 +509,8 @@ class IMAmpAgent:
         self.set_eval()
         e = self.exp
         task = self.task
-        if getattr(self, "_terminated_flags", None) is None:
+        if self._terminated_flags is None:
             self._terminated_flags = torch.zeros(self.num_actors, device=self.device)
-            self._reward_raw_acc = None
-            self._roll_graphs, self._roll_pool = {}, None
             self._env_actions = torch.empty_like(self.exp["actions"][0])
         terminated_flags = self._terminated_flags.zero_()
         if self._reward_raw_acc is not None:
@@ -506,7 +519,7 @@ class IMAmpAgent:
         # says any of them moved (resample_motions(), evaluate() swapping libraries, flipped evaluation flags), every captured graph is dropped and
         # re-captured against the new objects (tests/test_env_gpu.py::test_rollout_graphs_follow_resample_motions_and_evaluate)
         gen = task.launch_generation() if hasattr(task, "launch_generation") else None
-        if gen != getattr(self, "_roll_generation", None):
+        if gen != self._roll_generation:
             if self._roll_graphs:
                 torch.cuda.synchronize()
                 self._roll_graphs.clear()
@@ -544,7 +557,7 @@ class IMAmpAgent:
             dev_ok = (rewards.is_cuda and rewards.dtype == torch.float32 and rewards.is_contiguous() and self.dones.dtype == torch.int64
                       and terminate.dtype == torch.int64 and reward_raw.dtype == torch.float32 and reward_raw.is_contiguous() and reward_raw.shape[1] <= 8)
             if dev_ok:   # rewards / dones / terminated flags / reward means / episode statistics in one launch (phc_rollout_bookkeeping)
-                if getattr(self, "_terminated_mask", None) is None:
+                if self._terminated_mask is None:
                     self._terminated_mask = torch.zeros(self.num_actors, dtype=torch.float32, device=self.device)
                 terminated = self._terminated_mask
                 L.check(L.load().phc_rollout_bookkeeping(
@@ -576,7 +589,7 @@ class IMAmpAgent:
             task.align_amp_window()
 
             def whole_step(n):
-                if n > 0 or self._reset_at_rollout_start:   # (step 0 resets nothing: see the eager loop below)
+                if n > 0:   # (step 0 resets nothing: see the eager loop below)
                     task.reset_done()
                 self.obs = task.obs_buf
                 seg_policy(n)
@@ -589,7 +602,7 @@ class IMAmpAgent:
                 key = ("step", n) + task.rollout_step_key()
                 if key in self._roll_graphs:
                     self._roll_graphs[key].replay()
-                    task.replay_step_host(reset=n > 0 or self._reset_at_rollout_start)
+                    task.replay_step_host(reset=n > 0)
                 else:
                     self._replay(key, lambda: whole_step(n))   # capture (runs the task's own host bookkeeping), then the first replay: no bookkeeping
             self.obs, self.dones = task.obs_buf, task.reset_buf
@@ -601,7 +614,7 @@ class IMAmpAgent:
                 # rollout are not reset at step 0 -- they run one more step, are flagged again by that step's `_compute_reset` (their clip is still over /
                 # they are still down) and are reset at step 1.  Kept: one in `horizon_length` episode ends carries that extra transition in the reference's
                 # data too (tests/test_learner_epoch.py pins it).
-                if n > 0 or self._reset_at_rollout_start:
+                if n > 0:
                     task.reset_done()
                 if np.isfinite(self.vec_env.clip_obs):   # clamp straight into the experience buffer row
                     self.obs = torch.clamp(task.obs_buf, -self.vec_env.clip_obs, self.vec_env.clip_obs, out=e["obses"][n])
@@ -694,19 +707,22 @@ class IMAmpAgent:
                         "actions": b["actions"], "obs": b["obses"], "mu": b["mus"], "sigma": b["sigmas"], "amp_obs": b["amp_obs"],
                         "amp_obs_demo": b["amp_obs_demo"], "amp_obs_replay": b["amp_obs_replay"]}
 
+    def _draw_rows(self, i, out=None):
+        """The dataset rows of minibatch `i` of the current pass over the batch (AMPDataset._get_item / _shuffle_idx_buf, amp_datasets.py:72-99), as a copy
+        or written into `out`: `_idx_buf` is re-drawn behind the last minibatch of a pass, before that minibatch's kernels have run."""
+        s, e = i * self.minibatch_size, (i + 1) * self.minibatch_size
+        rows = self._idx_buf[s:e].clone() if out is None else out.copy_(self._idx_buf[s:e])
+        if e >= self.batch_size:
+            self._idx_buf[:] = torch.randperm(self.batch_size, device=self._idx_buf.device)
+        return rows
+
     def _get_item(self, idx):
-        s, e = idx * self.minibatch_size, (idx + 1) * self.minibatch_size
-        sample_idx = self._idx_buf[s:e]
+        sample_idx = self._draw_rows(idx)
         amp_idx = sample_idx[:self._amp_minibatch_size]  # calc_gradients only reads rows [0:amp_minibatch_size] (amp_agent.py:570-577)
         if sample_idx.is_cuda:
             # the device kernels read the dataset rows in place (phc_running_norm / phc_ppo_loss take the row index): nothing is gathered
-            sample_idx = sample_idx.clone()   # _idx_buf is re-drawn below, before this minibatch's kernels have run
-            out = {"_dataset": self.dataset, "_idx": sample_idx, "_amp_idx": sample_idx[:self._amp_minibatch_size]}
-        else:
-            out = {k: v[amp_idx if k.startswith("amp_obs") else sample_idx] for k, v in self.dataset.items()}
-        if e >= self.batch_size:
-            self._idx_buf[:] = torch.randperm(self.batch_size, device=self._idx_buf.device)
-        return out
+            return {"_dataset": self.dataset, "_idx": sample_idx, "_amp_idx": amp_idx}
+        return {k: v[amp_idx if k.startswith("amp_obs") else sample_idx] for k, v in self.dataset.items()}
 
     # ------------------------------------------------------------------ losses (common_agent.py:512-520,564-587; amp_agent.py:732-808)
     def bound_loss(self, mu):
@@ -745,7 +761,7 @@ class IMAmpAgent:
 
     def _raw_buffer(self):
         nw = len(self.model.a2c_network.get_disc_weights_raw())
-        if getattr(self, "_raw", None) is None or self._raw.numel() != self._RAW_FIXED + nw:
+        if self._raw is None or self._raw.numel() != self._RAW_FIXED + nw:
             self._raw = torch.zeros(self._RAW_FIXED + nw, dtype=torch.float32, device=self.device)
         return self._raw, nw
 
@@ -758,127 +774,106 @@ class IMAmpAgent:
 
     def _disc_loss_fused(self, logits, m, obs_demo):
         """`_disc_loss` on the device with the pieces as kernels (fast_ops.disc_bce / weighted_sumsq): every term already carries
-        `disc_coef` and enters the total loss with weight one.  `logits` [3m, 1]: agent, replay, demo rows.
-        -> (the three loss terms, [(weight, c)] whose gradient c * weight is to be preloaded by FlatGradBucket.zero)."""
+        `disc_coef` and enters the total loss with weight one.  `logits` [3m, 1]: agent, replay, demo rows.  -> the three loss terms; where
+        `_disc_decay_terms` gives a preload, the gradient of the weight terms is not theirs to produce: FlatGradBucket.zero has written it."""
         k = self._disc_coef
         raw, nw = self._raw_buffer()
         bce, _ = disc_bce(logits, 2 * m, k, out=raw[7:12])
         ws, coefs, preload = self._disc_decay_terms()
         # (a K-padded weight enters with its padded storage -- the pad is zero --, when its gradient is preloaded anyway)
-        l2 = weighted_sumsq([getattr(w, "_padded", w) if preload else w.contiguous() for w in ws], coefs, out=raw[12:13 + nw], preloaded=preload)
+        l2 = weighted_sumsq([getattr(w, "_padded", w) if preload is not None else w.contiguous() for w in ws], coefs, out=raw[12:13 + nw], preloaded=preload is not None)
         # d(sum of the demo logits) / d(demo rows): cotangent = [0; 0; 1] over the [agent; replay; demo] logits, and the layers are told
         # that only the last row block carries anything (GEMMs over m instead of 3m rows, here and in the second-order pass)
         with input_grad_only(row_start=2 * m):
             grad = torch.autograd.grad(logits, obs_demo, grad_outputs=self._demo_row_mask(m, logits), create_graph=True, retain_graph=True,
                                        only_inputs=True)[0]
         pen = weighted_sumsq([grad], [self._disc_grad_penalty * k / m], out=raw[13 + nw:15 + nw])
-        return [bce, l2, pen], ([(w, 2.0 * c) for w, c in zip(ws, coefs)] if preload else None)
+        return [bce, l2, pen]
 
     def _disc_decay_terms(self):
-        """(discriminator weights, coefficient of each one's sum of squares in the total loss, whether their gradients 2 c w can be preloaded
-        into the flat bucket)."""
+        """(discriminator weights, coefficient of each one's sum of squares in the total loss, the preload: [(weight, 2 c)] for FlatGradBucket.zero
+        to start each weight's gradient at these terms' gradient 2 c w -- None where a weight is outside the flat bucket and autograd has to add it)."""
         k = self._disc_coef
         ws = [p for p in self.model.a2c_network.get_disc_weights_raw()]
         coefs = [self._disc_weight_decay * k] * len(ws)
         coefs[-1] += self._disc_logit_reg * k   # the logit layer: regulariser + weight decay
-        return ws, coefs, all(getattr(w, "_bucket", None) is self.grads for w in ws)
+        in_bucket = all(getattr(w, "_bucket", None) is self.grads for w in ws)
+        return ws, coefs, ([(w, 2.0 * c) for w, c in zip(ws, coefs)] if in_bucket else None)
 
     def _demo_row_mask(self, m, like):
         key = (m, like.dtype, like.device)
-        if getattr(self, "_ones_key", None) != key:
+        if self._ones_key != key:
             mask = torch.zeros((3 * m, 1), dtype=like.dtype, device=like.device)
             mask[2 * m:] = 1
             self._ones_key, self._ones = key, mask
         return self._ones
 
     def _fwd_bwd(self, d, want_info=True):
-        """Forward + losses + backward into the flat gradient bucket (amp_agent.py:554-655); no host sync.  `want_info=False` (the
-        captured step): when all scalars are in `self._raw` the info dict is not built (it would cost launches)."""
+        """Forward + losses + backward into the flat gradient bucket (amp_agent.py:554-655); no host sync.  -> (info dict, whether the
+        gradient was all-reduced on the way).  `want_info=False` (a pass of the captured update outside its graphs' replay): no collective,
+        and when all scalars are in `self._raw` the info dict is not built (it would cost launches)."""
         idx = amp_idx = None
         if "_dataset" in d:   # device: minibatch = (dataset, row index); the kernels below read the rows in place
             d, idx, amp_idx = d["_dataset"], d["_idx"], d["_amp_idx"]
-        br = self._branch_streams(d["obs"].device) if (d["obs"].is_cuda and self._disc_grad_penalty > 0 and self._normalize_amp_input) else None
-        if br:
-            # the discriminator pass on its stream next to the policy pass: see __init__
-            main = torch.cuda.current_stream(d["obs"].device)
-            br.wait_stream(main)
-            split = self._split_active() and want_info      # (want_info=False: a captured step's warm-up pass -- gradients only, no collective)
-            with torch.cuda.stream(br):
-                self._disc_pass(d, amp_idx)
-                if split:
-                    self._grad_all_reduce("disc")
-            self._policy_pass(d, idx)
-            if split:
-                self._grad_all_reduce("policy")
-            self._reduced_in_pass = split
-            main.wait_stream(br)
-            return self._info_from_raw(self._raw.clone()) if want_info else None   # (a copy: the next step overwrites `_raw`)
+        if self._fused_disc:
+            reduced = self._device_step(d, idx, amp_idx, collectives=want_info)
+            return (self._info_from_raw(self._raw.clone()) if want_info else None), reduced   # (a copy: the next step overwrites `_raw`)
+        # the torch path: the CPU, and the device when the fused discriminator loss does not apply (there with the fused actor / critic loss)
         obs = self._preproc_obs(d["obs"], use_temp=self.temp_running_mean, row_index=idx)
         fused = obs.is_cuda
-        fused_disc = fused and self._disc_grad_penalty > 0 and self._normalize_amp_input
-        if fused_disc:
-            # the normaliser writes the three AMP batches into the row blocks of ONE [agent; replay; demo] buffer (no torch.cat in front
-            # of the discriminator); the demo block is also the leaf the gradient penalty differentiates to
-            m = amp_idx.numel() if amp_idx is not None else d["amp_obs"].shape[0]
-            dt = torch.bfloat16 if self.bf16 else torch.float32
-            A = d["amp_obs"].shape[1]
-            if self.bf16 and getattr(self, "_amp_pad_cols", 0) > A:   # K-padded discriminator input (pad columns stay zero)
-                cat = self._pad_buf("amp_cat", 3 * m, self._amp_pad_cols)
-            else:
-                cat = torch.empty((3 * m, A), dtype=dt, device=obs.device)
-            for k, key in enumerate(("amp_obs", "amp_obs_replay", "amp_obs_demo")):
-                self._amp_input_mean_std(d[key], out_dtype=dt, row_index=amp_idx, out=cat[k * m:(k + 1) * m, :A])
-            amp_obs = cat[:m]
-            amp_obs_demo = cat[2 * m:].requires_grad_(True)
-            inp = {"is_train": True, "obs": obs, "amp_obs_cat": rows_with_grad(cat, amp_obs_demo, 2 * m), "raw_disc_logits": True}
-        else:
-            amp_obs = self._preproc_amp_obs(d["amp_obs"], amp_idx)
-            amp_obs_replay = self._preproc_amp_obs(d["amp_obs_replay"], amp_idx)
-            amp_obs_demo = self._preproc_amp_obs(d["amp_obs_demo"], amp_idx)
-            amp_obs_demo.requires_grad_(True)
-            inp = {"is_train": True, "prev_actions": d["actions"], "obs": obs, "amp_obs": amp_obs, "amp_obs_replay": amp_obs_replay,
-                   "amp_obs_demo": amp_obs_demo, "raw_disc_logits": False}
+        amp_obs, amp_obs_replay, amp_obs_demo = (self._preproc_amp_obs(d[k], amp_idx) for k in ("amp_obs", "amp_obs_replay", "amp_obs_demo"))
+        amp_obs_demo.requires_grad_(True)
+        inp = {"is_train": True, "prev_actions": d["actions"], "obs": obs, "amp_obs": amp_obs, "amp_obs_replay": amp_obs_replay,
+               "amp_obs_demo": amp_obs_demo, "raw_disc_logits": False}
         if self._actor_split and fused:
             inp["obs_actor"] = self._actor_obs(d["obs"], use_temp=self.temp_running_mean, row_index=idx)
         with self._autocast():
             res = self.model.forward_heads(inp) if fused else self.model(inp)
-        if self._actor_split and fused:
-            res["value"] = res["value"].float()
-        decay = None
-        if fused_disc:
-            roots, decay = self._disc_loss_fused(res["disc_logits"], amp_obs.shape[0], amp_obs_demo)
-            disc_info = None
-        else:
-            disc_info = self._disc_loss(torch.cat([res["disc_agent_logit"], res["disc_agent_replay_logit"]], dim=0), res["disc_demo_logit"], amp_obs_demo)
-            roots = [self._disc_coef * disc_info["disc_loss"]]
+        disc_info = self._disc_loss(torch.cat([res["disc_agent_logit"], res["disc_agent_replay_logit"]], dim=0), res["disc_demo_logit"], amp_obs_demo)
         if fused:
-            # actor / critic losses and their gradients w.r.t. the two heads: one HIP pass (phc_ppo_loss) instead of ~100 launches
-            ppo, st = ppo_loss(res["mu"].contiguous(), res["value"].contiguous(), res["logstd"], d["actions"], d["old_logp_actions"], d["advantages"],
-                               d["returns"], d["old_values"], d["mu"], d["sigma"], self.e_clip, self.critic_coef, self.entropy_coef,
-                               self.bounds_loss_coef, self.clip_value, unit_grad=True, row_index=idx, out=self._raw_buffer()[0][0:7])
-            # `ppo` and the fused discriminator terms enter the total with weight one (unit_grad): they are the roots of ONE backward
-            # pass with constant unit cotangents -- no sum node, no fill launches
-            roots = [ppo] + roots
-            info = None if fused_disc else {"actor_loss": st[0], "critic_loss": st[1], "b_loss": st[2], "entropy": st[3], "kl": st[4], "actor_clip_frac": st[5]}
-            self.grads.zero(decay)
-            with param_grad_only(), deferred_colsums():
-                torch.autograd.backward(roots, grad_tensors=[self._unit_cotangent(r) for r in roots])
+            disc = self._disc_coef * disc_info["disc_loss"]
+            ppo, st = self._ppo_loss_fused(res["mu"], res["value"], res["logstd"], d, idx)
+            info = {"actor_loss": st[0], "critic_loss": st[1], "b_loss": st[2], "entropy": st[3], "kl": st[4], "actor_clip_frac": st[5]}
+            self.grads.zero()
+            self._backward([ppo, disc])
         else:
             assert idx is None
             loss, info = self._ppo_loss_torch(res, d, disc_info)
             self.grads.zero()
             loss.backward()
-        if info is None:   # everything is in the raw vector
-            return self._info_from_raw(self._raw.clone()) if want_info else None   # (a copy: the next step overwrites `_raw`)
         info.update({k: (v.detach() if torch.is_tensor(v) else v) for k, v in disc_info.items()})
-        return info
+        return info, False
 
-    def _branch_streams(self, device):
-        """The discriminator's stream of the optimizer step, or None (CPU, switched off)."""
-        if not self._use_branches or torch.device(device).type != "cuda":
+    def _device_step(self, d, idx, amp_idx, collectives=True):
+        """The device's forward + backward of one optimizer step: `_policy_pass` and `_disc_pass`, side by side on two streams or one after the
+        other on the current one.  Every scalar lands in `self._raw`.  -> whether the gradient was all-reduced behind the passes."""
+        br = self._branch_streams()
+        if br is None:
+            # ONE zero of the whole bucket, with the weight-decay preload, in front of both bodies: a second zero() between the preload and the
+            # discriminator's backward would bump the bucket's generation and make that backward overwrite the preload (fast_ops._first_write)
+            self.grads.zero(self._disc_decay_terms()[2])
+            self._policy_pass(d, idx, zero=False)
+            self._disc_pass(d, amp_idx, zero=False)
+            return False
+        # the discriminator pass on its stream next to the policy pass: see __init__
+        main = torch.cuda.current_stream(self.device)
+        br.wait_stream(main)
+        split = collectives and self._split_active()
+        with torch.cuda.stream(br):
+            self._disc_pass(d, amp_idx)
+            if split:
+                self._grad_all_reduce("disc")
+        self._policy_pass(d, idx)
+        if split:
+            self._grad_all_reduce("policy")
+        main.wait_stream(br)
+        return split
+
+    def _branch_streams(self):
+        """The discriminator's stream of the optimizer step, or None (switched off)."""
+        if not self._use_branches:
             return None
         if self._branches is None:
-            from .fast_ops import register_lane
             net = self.model.a2c_network
             disc_params = [p for mod in (net._disc_mlp, net._disc_logits) for p in mod.parameters()]
             try:
@@ -886,57 +881,68 @@ class IMAmpAgent:
             except ValueError:      # (a network whose discriminator parameters are not one run of the bucket: one stream, as before round 4)
                 self._use_branches = False
                 return None
-            self._branches = torch.cuda.Stream(device)
+            self._branches = torch.cuda.Stream(self.device)
             register_lane(self._branches, "disc")      # (its kernels get their own reduction scratch buffers)
         return self._branches
 
-    def _disc_pass(self, d, amp_idx):
-        """The discriminator's share of an optimizer step on the CURRENT stream: its slice of the gradient bucket zeroed (weight-decay gradients
-        preloaded), the three AMP batches normalised into one [agent; replay; demo] buffer, forward, loss terms, backward."""
-        ws, coefs, preload = self._disc_decay_terms()
-        self.grads.zero([(w, 2.0 * c) for w, c in zip(ws, coefs)] if preload else None, spans=self._disc_spans)
+    def _amp_cat(self, d, amp_idx):
+        """The three AMP batches normalised into the row blocks of ONE [agent; replay; demo] buffer (no torch.cat in front of the
+        discriminator); the demo block is also the leaf the gradient penalty differentiates to.  -> (buffer, demo leaf, rows per block)"""
         m = amp_idx.numel() if amp_idx is not None else d["amp_obs"].shape[0]
         dt = torch.bfloat16 if self.bf16 else torch.float32
         A = d["amp_obs"].shape[1]
-        if self.bf16 and getattr(self, "_amp_pad_cols", 0) > A:   # K-padded discriminator input (pad columns stay zero)
+        if self.bf16 and self._amp_pad_cols > A:   # K-padded discriminator input (pad columns stay zero)
             cat = self._pad_buf("amp_cat", 3 * m, self._amp_pad_cols)
         else:
             cat = torch.empty((3 * m, A), dtype=dt, device=d["amp_obs"].device)
         for k, key in enumerate(("amp_obs", "amp_obs_replay", "amp_obs_demo")):
             self._amp_input_mean_std(d[key], out_dtype=dt, row_index=amp_idx, out=cat[k * m:(k + 1) * m, :A])
-        amp_obs_demo = cat[2 * m:].requires_grad_(True)
+        return cat, cat[2 * m:].requires_grad_(True), m
+
+    def _disc_pass(self, d, amp_idx, zero=True):
+        """The discriminator's share of an optimizer step on the CURRENT stream: the three AMP batches normalised into one
+        [agent; replay; demo] buffer, forward, loss terms, backward.  `zero`: its slice of the gradient bucket is zeroed first (weight-decay
+        gradients preloaded); False when the caller has zeroed the whole bucket for both passes."""
+        if zero:
+            self.grads.zero(self._disc_decay_terms()[2], spans=self._disc_spans)
+        cat, amp_obs_demo, m = self._amp_cat(d, amp_idx)
         with self._autocast():
             logits = self.model.a2c_network.eval_disc(rows_with_grad(cat, amp_obs_demo, 2 * m))
-        roots, _ = self._disc_loss_fused(logits, m, amp_obs_demo)
-        with param_grad_only(), deferred_colsums():   # (bias gradients: first stages in the layers, ONE finishing launch here)
-            torch.autograd.backward(roots, grad_tensors=[self._unit_cotangent(r) for r in roots])
+        self._backward(self._disc_loss_fused(logits, m, amp_obs_demo))
 
-    def _policy_pass(self, d, idx):
-        """Actor + critic share of an optimizer step on the current stream: their slices of the gradient bucket zeroed, the observation
+    def _policy_pass(self, d, idx, zero=True):
+        """Actor + critic share of an optimizer step on the current stream: (`zero`) their slices of the gradient bucket zeroed, the observation
         normalised, both forward passes, the fused loss kernel, backward.  (The critic on a third stream was measured too: a graph with a
         fork inside leaves the runtime's packet-replay path -- profiles/r04_ppo/README.md.)"""
         net = self.model.a2c_network
-        self.grads.zero(spans=self._policy_spans)
+        if zero:
+            self.grads.zero(spans=self._policy_spans)
         obs = self._preproc_obs(d["obs"], use_temp=self.temp_running_mean, row_index=idx)
         with self._autocast():
             value = net.eval_critic(obs)
             mu, logstd = net.eval_actor(self._actor_obs(d["obs"], use_temp=self.temp_running_mean, row_index=idx) if self._actor_split else obs)
+        self._backward([self._ppo_loss_fused(mu, value, logstd[0] if logstd.dim() == 2 else logstd, d, idx)[0]])
+
+    def _ppo_loss_fused(self, mu, value, logstd, d, idx):
+        """Actor / critic losses and their gradients w.r.t. the two heads: one HIP pass (phc_ppo_loss) instead of ~100 launches.
+        -> (loss root, its six statistics); the scalars also land in `_raw[0:7]`."""
         if self._actor_split:
             value = value.float()           # (phc_ppo_loss takes both heads in one type)
-        ppo, _ = ppo_loss(mu.contiguous(), value.contiguous(), logstd[0] if logstd.dim() == 2 else logstd, d["actions"], d["old_logp_actions"],
-                          d["advantages"], d["returns"], d["old_values"], d["mu"], d["sigma"], self.e_clip, self.critic_coef, self.entropy_coef,
-                          self.bounds_loss_coef, self.clip_value, unit_grad=True, row_index=idx, out=self._raw_buffer()[0][0:7])
+        return ppo_loss(mu.contiguous(), value.contiguous(), logstd, d["actions"], d["old_logp_actions"], d["advantages"], d["returns"],
+                        d["old_values"], d["mu"], d["sigma"], self.e_clip, self.critic_coef, self.entropy_coef, self.bounds_loss_coef,
+                        self.clip_value, unit_grad=True, row_index=idx, out=self._raw_buffer()[0][0:7])
+
+    def _backward(self, roots):
+        """The fused loss terms enter the total with weight one (unit_grad): they are the roots of ONE backward pass with constant unit
+        cotangents -- no sum node, no fill launches.  Bias gradients: first stages in the layers, ONE finishing launch at the end."""
         with param_grad_only(), deferred_colsums():
-            torch.autograd.backward([ppo], grad_tensors=[self._unit_cotangent(ppo)])
+            torch.autograd.backward(roots, grad_tensors=[self._unit_cotangent(r) for r in roots])
 
     def _unit_cotangent(self, like):
         key = (like.dtype, like.device)
-        c = getattr(self, "_unit_cot", None)
-        if c is None:
-            c = self._unit_cot = {}
-        if key not in c:
-            c[key] = torch.ones((), dtype=like.dtype, device=like.device)
-        return c[key]
+        if key not in self._unit_cot:
+            self._unit_cot[key] = torch.ones((), dtype=like.dtype, device=like.device)
+        return self._unit_cot[key]
 
     def _ppo_loss_torch(self, res, d, disc_info):
         """The actor / critic losses as torch expressions (amp_agent.py:598-640): the CPU path and the definition `phc_ppo_loss` is
@@ -971,251 +977,44 @@ class IMAmpAgent:
             self.grads.clip_grad_norm_(self.grad_norm)
         self.optimizer.step()
 
-    def _amp_rows(self, d):
-        m = self._amp_minibatch_size
-        if "_dataset" in d:
-            return d
-        return {k: (v[0:m] if k.startswith("amp_obs") else v) for k, v in d.items()}
-
     def calc_gradients(self, d):
         """One optimizer step (amp_agent.py:554-688): forward/backward, the path's one collective -- the flat gradient
         all-reduce, replacing `optimizer.synchronize()` (:667-668) -- then clip + Adam on the flat parameter."""
         self.set_train()
-        d = self._amp_rows(d)
-        self._reduced_in_pass = False
-        info = self._fwd_bwd(d)
-        if not self._reduced_in_pass:
+        if "_dataset" not in d:   # a gathered minibatch: only rows [0:amp_minibatch_size] of the AMP batches are read (amp_agent.py:570-577)
+            d = {k: (v[0:self._amp_minibatch_size] if k.startswith("amp_obs") else v) for k, v in d.items()}
+        info, reduced = self._fwd_bwd(d)
+        if not reduced:
             self._grad_all_reduce()
-        restore = self._debug_freeze(self._step_in_epoch) if self._debug_groups() else None
         self._clip_and_step()
-        if restore is not None:
-            restore()
-        self._step_in_epoch += 1
         return info
-
-    # ---- diagnostic knobs (VERDICT r5 item 1d): `+learning.params.config.debug_actor_steps=K` (`debug_critic_steps`, `debug_disc_steps`) lets that network take only the
-    # FIRST K optimizer steps of every epoch -- what `mini_epochs` does for all three at once, separately.  On the other steps the group's gradient is zeroed before
-    # the clip and its parameters + Adam moments are put back after the step (the optimizer kernel works on the whole flat parameter).  Eager launches only.
-    def _debug_groups(self):
-        if getattr(self, "_dbg", None) is None:
-            c, self._dbg = self.config, {}
-            names = {id(p): n for n, p in self.model.named_parameters()}
-            for grp, key in (("actor", "debug_actor_steps"), ("critic", "debug_critic_steps"), ("disc", "debug_disc_steps")):
-                if c.get(key) is None:
-                    continue
-                of = lambda n: "disc" if "_disc" in n else ("critic" if ("critic" in n or ".value." in n) else "actor")
-                spans = [(o, o + k) for p, (o, k) in zip(self.grads.params, self.grads.segments) if of(names[id(p)]) == grp]
-                self._dbg[grp] = (int(c[key]), spans)
-        return self._dbg
-
-    def _debug_freeze(self, step_in_epoch):
-        """-> restore() for the groups that sit this step out (None when every group steps)."""
-        off = [spans for k, spans in self._debug_groups().values() if step_in_epoch >= k]
-        if not off:
-            return None
-        from .fast_ops import adam_state
-        st = adam_state(self.optimizer, self.grads.flat_param) if self.grads.flat.is_cuda else self.optimizer.state.get(self.grads.flat_param, {})
-        bufs = [self.grads.flat_param] + [st[k] for k in ("exp_avg", "exp_avg_sq") if k in st]
-        saved = []
-        for spans in off:
-            for lo, hi in spans:
-                self.grads.flat[lo:hi].zero_()
-                saved.append((lo, hi, [b[lo:hi].clone() for b in bufs]))
-
-        def restore():
-            for lo, hi, vals in saved:
-                for b, v in zip(bufs, vals):
-                    b[lo:hi].copy_(v)
-            if self.grads.shadow is not None:
-                self.grads.shadow.copy_(self.grads.flat_param)
-        return restore
 
     def _grad_all_reduce(self, part=None):
         """`part` None: the whole flat gradient (one collective per optimizer step, the default).  "disc" / "policy" (`split_allreduce`): that pass's range of the
         bucket, issued on the CURRENT stream right behind the pass -- the discriminator's all-reduce then runs while the (longer) policy chain is still computing."""
-        if self.multi_gpu or (self._force_collectives and self.dist is not None):
+        if self._reduces:
             spans = None if part is None else (self._disc_spans if part == "disc" else self._policy_spans)
             self.num_collectives += self.grads.all_reduce_mean(self.dist, force=self._force_collectives, timing=self.allreduce_timing, spans=spans)
 
     def _split_active(self):
         """Two all-reduces per optimizer step instead of one (`+learning.params.config.split_allreduce=True`; needs the two-stream step)."""
-        return (self._split_allreduce and (self.multi_gpu or (self._force_collectives and self.dist is not None)) and self._branches is not None)
+        return self._split_allreduce and self._reduces and self._branches is not None
 
-    # ------------------------------------------------------------------ the optimizer step as a hipGraph
-    # With the loss, normaliser and optimizer kernels fused, a step is ~140 launches of 2 ms total device time and the host needs
-    # 2.7-3.9 ms to issue them (it varies with the box): launch-bound.  Device runs can therefore capture the forward / backward part of
-    # ONE step -- minibatch given by a row-index buffer into persistent dataset tensors -- and replay it 48 times per epoch; the
-    # gradient all-reduce (multi-GPU) and the two optimizer launches follow each replay eagerly, so the graph holds no collective.
+    # ------------------------------------------------------------------ the optimizer step as a hipGraph (update_graph.CapturedUpdate)
     def _graph_enabled(self):
-        return (self.grads.flat.is_cuda and self._use_graph and not self._graph_failed and not self._debug_groups() and self.minibatch_size >= int(self.config.get("hip_graph_min_rows", 2048))
+        return (self.grads.flat.is_cuda and self._use_graph and not self._graph_failed and self.minibatch_size >= int(self.config.get("hip_graph_min_rows", 2048))
                 and not os.environ.get("PHC_NO_GRAPH"))
 
-    def _stale_grad_accumulators(self):
-        """True if some parameter's AccumulateGrad node is kept alive by a graph outside this update (e.g. `w0 = p.clone()` held by
-        the caller): such a node is bound to the stream it was created on and breaks stream capture.  A parameter caches its
-        accumulator weakly, so a node nobody else holds is gone once we drop it -- a tag we leave on it tells the two cases apart."""
-        from torch.autograd.graph import get_gradient_edge
-        for p in self.grads.params:
-            get_gradient_edge(p).node.metadata["phc_probe"] = True
-        return any("phc_probe" in get_gradient_edge(p).node.metadata for p in self.grads.params)
+    @property
+    def update_graphs(self):    # hipGraphs one captured optimizer step replays: 0 (eager launches), 1, or 3 (policy pass, discriminator pass, tail)
+        return self._update.num_graphs
 
-    def _graph_static_dataset(self):
-        """The dataset of this epoch behind fixed addresses (a captured graph keeps reading the same buffers)."""
-        if self._g_data is None:
-            # the tensors of the first graphed epoch BECOME the persistent buffers (the dict keeps them alive): rollout-buffer views
-            # keep their address from epoch to epoch and are never copied, per-epoch temporaries are copied into these
-            self._g_data, seen = {}, set()
-            for k, v in self.dataset.items():   # (two keys may share one tensor: the replay batch IS the agent batch while the buffer is empty)
-                self._g_data[k] = v.clone() if v.data_ptr() in seen else v
-                seen.add(v.data_ptr())
-        for k, v in self.dataset.items():
-            g = self._g_data[k]
-            if g.shape != v.shape:
-                raise RuntimeError("dataset shape changed under a captured update graph")
-            if g.data_ptr() != v.data_ptr():
-                g.copy_(v)
-        return self._g_data
+    @property
+    def update_streams(self):   # 2 once an optimizer step has run its discriminator pass on a stream of its own, else 1
+        return 2 if self._branches is not None else 1
 
-    def _graph_step_body(self):
-        info = self._fwd_bwd({"_dataset": self._g_data, "_idx": self._g_idx, "_amp_idx": self._g_idx[:self._amp_minibatch_size]}, want_info=False)
-        if info is None:     # raw vector of the fused kernels (see _raw_buffer): one launch
-            self._g_keys = None
-            if self._g_info.numel() != self._raw.numel():
-                self._g_info = torch.zeros_like(self._raw)
-            self._g_info += self._raw
-            return
-        self._g_keys = list(info)
-        self._g_info += torch.stack([info[k].float().reshape(()) for k in self._g_keys])
-
-    def _graph_tail(self, fuse_opt):
-        """Behind the two passes of a branched step: the step's scalars into the epoch's accumulator, clip + Adam (one rank)."""
-        self._g_keys = None
-        if self._g_info.numel() != self._raw.numel():
-            self._g_info = torch.zeros_like(self._raw)
-        self._g_info += self._raw
-        if fuse_opt:
-            self._clip_and_step(step_device=self._g_step)
-
-    def _graph_opt_key(self):
-        """What a graph with the optimizer step inside has baked in: a change (checkpoint with another lr, ...) forces a re-capture."""
-        g = self.optimizer.param_groups[0]
-        collectives = self.multi_gpu or (self._force_collectives and self.dist is not None) or bool(os.environ.get("PHC_NO_OPT_IN_GRAPH"))
-        return (not collectives, float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), self.grad_norm if self.truncate_grads else None)
-
-    def _graph_update(self):
-        """All mini-epochs of one epoch through the captured forward / backward; returns the mean info dict (device tensors).
-        One rank (no collective between backward and optimizer): the clip + Adam launches are part of the captured step as well -- a step is
-        then the row-index copy and ONE replay, which takes the host out of the loop (on a freshly started box the eager launches between
-        the replays cost ~10 % of the update: 69 vs 62 ms)."""
-        self.set_train()
-        self._graph_static_dataset()
-        key = self._graph_opt_key()
-        if self._graph is not None and getattr(self, "_graph_key", None) != key:
-            self._graph = None
-        fuse_opt = key[0]
-        from .fast_ops import adam_state, _workspace
-        adam_state(self.optimizer, self.grads.flat_param)      # exists before any capture
-        _workspace("adam", L.load().phc_adam_workspace(), self.grads.flat_param.device, torch.float64)
-        if self._g_idx is None:
-            self._g_idx = torch.zeros(self.minibatch_size, dtype=torch.int64, device=self.device)
-            self._g_info = torch.zeros(len(self._probe_info_keys()), dtype=torch.float32, device=self.device)
-        if self._graph is None:
-            if self._stale_grad_accumulators():
-                raise RuntimeError("an autograd graph outside the update holds a parameter's gradient accumulator (e.g. `p.clone()` kept "
-                                   "alive: use `p.detach().clone()`); stream capture would crash")
-            self._g_idx.copy_(self._idx_buf[:self.minibatch_size])
-            # the warm-up passes torch asks for before a capture must not train: they only touch the gradients (zeroed by every step)
-            # and the normaliser statistics, which are restored afterwards
-            norms = [(m, [b.clone() for b in m.buffers()]) for m in self._norms()]
-            try:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._graph_step_body()
-                torch.cuda.current_stream().wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                # with a process group alive its watchdog thread polls events while we capture: thread-local capture mode keeps
-                # those calls from invalidating the capture (the graph itself holds no collective)
-                in_group = self.dist is not None and self.dist.is_initialized()
-                if in_group:   # nothing of the group may be in flight on this device while the capture starts
-                    torch.cuda.synchronize()
-                    self.dist.barrier()
-                    torch.cuda.synchronize()
-                if fuse_opt and getattr(self, "_g_step", None) is None:
-                    self._g_step = torch.zeros((), dtype=torch.int64, device=self.device)
-                mode = "thread_local" if in_group else "global"
-                br = self._branch_streams(self.device) if (self._disc_grad_penalty > 0 and self._normalize_amp_input) else None
-                if br:
-                    # three LINEAR graphs per step: the policy pass, the discriminator pass captured ON its stream, and the tail (scalars,
-                    # clip + Adam).  One graph with the passes as branches was measured first: a graph with a fork is enqueued node by node by
-                    # the host (286 vs 40 us per replay in scripts/probes/graph_branch_concurrency.py) in topological order, and the device
-                    # ran the chains mostly one after the other (profiles/r04_ppo/README.md)
-                    gd, gt = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                    data, m = self._g_data, self._amp_minibatch_size
-                    with torch.cuda.graph(g, capture_error_mode=mode):
-                        self._policy_pass(data, self._g_idx)
-                    with torch.cuda.graph(gd, stream=br, capture_error_mode=mode):
-                        self._disc_pass(data, self._g_idx[:m])
-                    with torch.cuda.graph(gt, capture_error_mode=mode):
-                        self._graph_tail(fuse_opt)
-                    g = (g, gd, gt)
-                else:
-                    with torch.cuda.graph(g, capture_error_mode=mode):
-                        self._graph_step_body()
-                        if fuse_opt:
-                            self._clip_and_step(step_device=self._g_step)
-            finally:
-                for m, bufs in norms:
-                    for b, k in zip(m.buffers(), bufs):
-                        b.copy_(k)
-            self._graph, self._graph_key = g, key
-        self._g_info.zero_()
-        st = self.optimizer.state[self.grads.flat_param]
-        if fuse_opt:   # the device step count follows the optimizer's (checkpoint restores, eager steps in between)
-            self._g_step.fill_(int(st["step"].item()))
-        n = 0
-        for _ in range(self.mini_epochs_num):
-            for i in range(self.num_minibatches):
-                s, e = i * self.minibatch_size, (i + 1) * self.minibatch_size
-                self._g_idx.copy_(self._idx_buf[s:e])
-                if e >= self.batch_size:
-                    self._idx_buf[:] = torch.randperm(self.batch_size, device=self._idx_buf.device)
-                if isinstance(self._graph, tuple):
-                    gp, gd, gt = self._graph
-                    main, sd = torch.cuda.current_stream(self.device), self._branches
-                    split = (not fuse_opt) and self._split_active()
-                    sd.wait_stream(main)
-                    with torch.cuda.stream(sd):
-                        gd.replay()
-                        if split:
-                            self._grad_all_reduce("disc")
-                    gp.replay()
-                    if split:
-                        self._grad_all_reduce("policy")
-                    main.wait_stream(sd)
-                    gt.replay()
-                else:
-                    split = False
-                    self._graph.replay()
-                if not fuse_opt:
-                    if not split:
-                        self._grad_all_reduce()
-                    self._clip_and_step()
-                if self._trace is not None and self._g_keys is None:
-                    inf = self._info_from_raw(self._raw.clone())
-                    self._trace.append(torch.stack([inf[k] for k in self._probe_info_keys()]))
-                n += 1
-        if fuse_opt:
-            st["step"] += n
-        mean = self._g_info / n
-        if self._g_keys is None:
-            return self._info_from_raw(mean)
-        return {k: mean[j] for j, k in enumerate(self._g_keys)}
-
-    def _probe_info_keys(self):
-        return ["actor_loss", "critic_loss", "b_loss", "entropy", "kl", "actor_clip_frac", "disc_loss", "disc_grad_penalty", "disc_logit_loss", "disc_agent_acc",
-                "disc_demo_acc", "disc_agent_logit", "disc_demo_logit"]
+    INFO_KEYS = ("actor_loss", "critic_loss", "b_loss", "entropy", "kl", "actor_clip_frac", "disc_loss", "disc_grad_penalty", "disc_logit_loss", "disc_agent_acc",
+                 "disc_demo_acc", "disc_agent_logit", "disc_demo_logit")
 
     # ------------------------------------------------------------------ epoch (amp_agent.py:413-532)
     def _init_amp_demo_buf(self):
@@ -1283,13 +1082,12 @@ class IMAmpAgent:
         self.set_train()
         self.prepare_dataset(batch)
         infos, ginfo = [], None
-        self._step_in_epoch = 0
         with self.grads.shadow_scope(), _marker("phc:update"):
             if self._graph_enabled():
                 try:
-                    ginfo = self._graph_update()
+                    ginfo = self._update.run_epoch()
                 except Exception as exc:   # capture not possible on this stack: eager launches from here on
-                    if self._graph is not None:
+                    if self._update.num_graphs:
                         raise
                     self._graph_failed = True
                     torch.cuda.synchronize()
@@ -1299,7 +1097,7 @@ class IMAmpAgent:
                     for i in range(self.num_minibatches):
                         infos.append(self.calc_gradients(self._get_item(i)))
                         if self._trace is not None:
-                            self._trace.append(torch.stack([infos[-1][k].float().reshape(()) for k in self._probe_info_keys()]))
+                            self._trace.append(torch.stack([infos[-1][k].float().reshape(()) for k in self.INFO_KEYS]))
         self._store_replay_amp_obs(batch["amp_obs"])
         self.post_epoch(self.epoch_num)
         sync()
@@ -1314,8 +1112,7 @@ class IMAmpAgent:
                     step_fps=self.batch_size / (t1 - t0), total_fps=self.batch_size / (t2 - t0))  # common_agent.py:134-138
         if self._trace is not None:   # `+learning.params.config.trace_minibatches=True`: every optimizer step's scalars, in order (a diagnostic)
             tr = torch.stack(self._trace).cpu() if self._trace else torch.zeros(0)
-            keys = self._probe_info_keys()
-            info["minibatch_trace"] = {k: tr[:, j].tolist() for j, k in enumerate(keys)} if tr.numel() else {}
+            info["minibatch_trace"] = {k: tr[:, j].tolist() for j, k in enumerate(self.INFO_KEYS)} if tr.numel() else {}
             self._trace = []
         return info
 
@@ -1342,7 +1139,7 @@ class IMAmpAgent:
         SummaryWriter can be made -- into event files next to it."""
         import json
         d = os.path.join(output_dir, "summaries")
-        if getattr(self, "_summary_file", None) is None:
+        if self._summary_file is None:
             os.makedirs(d, exist_ok=True)
             self._summary_file = open(os.path.join(d, "scalars.jsonl"), "a")
             try:

@@ -32,7 +32,7 @@ _lanes = {}        # raw stream handle -> lane name (register_lane): kernels on 
 
 
 def register_lane(stream, name):
-    """The optimizer step forks independent networks onto side streams (IMAmpAgent._fwd_bwd): launches issued while `stream` is current
+    """The optimizer step forks independent networks onto side streams (IMAmpAgent._device_step): launches issued while `stream` is current
     -- the forward under `torch.cuda.stream(stream)`, the backward because autograd runs a node on its forward's stream -- take their
     workspaces under `name`, so that two branches never share a reduction scratch buffer."""
     _lanes[stream.cuda_stream] = name
@@ -77,7 +77,7 @@ def _first_write(p):
 # ---- deferred second stage of the column sums (round 5) ---------------------------------------------------------------------------------
 # Inside `deferred_colsums()` a column sum that goes straight into a bucket gradient (`out` given) only runs its first stage; the per-chunk
 # partials wait in a workspace of their own (keyed by the destination) and ONE `phc_colsum_finish_batch` launch at the end of the pass finishes
-# all of them -- the agent's passes end with it (IMAmpAgent._policy_pass / _disc_pass / _fwd_bwd).  Nobody reads a bias gradient before clip + Adam.
+# all of them -- the agent's passes end with it (IMAmpAgent._backward, from _policy_pass / _disc_pass / _fwd_bwd).  Nobody reads a bias gradient before clip + Adam.
 # Module-level state, like `_INPUT_GRAD_ONLY`: the backward runs on the autograd engine's thread; the pending list is per lane (stream).
 _DEFER = [0]
 _pending = {}

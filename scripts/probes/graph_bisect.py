@@ -26,25 +26,25 @@ if len(sys.argv) > 1 and sys.argv[1] in STAGES:
                 return
             deep(k - 1)
         deep(int(os.environ.get("DEPTH", "400")))
-        print("graph" if ag._graph is not None else "eager", "ok")
+        print("graph" if ag.update_graphs else "eager", "ok")
         sys.exit(0)
     if stage == "G_as_test":
         ag.train_epoch()
-        print("graph" if ag._graph is not None else "eager", "ok")
+        print("graph" if ag.update_graphs else "eager", "ok")
         sys.exit(0)
     if stage == "F_train_epoch":
         del os.environ["PHC_NO_GRAPH"]
         for _ in range(2):
             info = ag.train_epoch()
-        print("graph" if ag._graph is not None else "eager", "ok")
+        print("graph" if ag.update_graphs else "eager", "ok")
         sys.exit(0)
     ag.set_train()
-    ag._graph_static_dataset()
-    ag._g_idx = ag._idx_buf[:ag.minibatch_size].clone()
-    ag._g_step = torch.zeros((), dtype=torch.int64, device=ag.device)
-    ag._g_info = torch.zeros(10, device=ag.device)
-    d = ag._g_data
-    idx, aidx = ag._g_idx, ag._g_idx[:ag._amp_minibatch_size]
+    up = ag._update          # (the captured update's static state, filled by hand: update_graph.CapturedUpdate)
+    up._refresh_dataset()
+    up.idx = ag._idx_buf[:ag.minibatch_size].clone()
+    up.acc = torch.zeros(len(ag.INFO_KEYS), device=ag.device)
+    d = up.data
+    idx, aidx = up.idx, up.idx[:ag._amp_minibatch_size]
     def body():
         obs = ag._preproc_obs(d["obs"], use_temp=ag.temp_running_mean, row_index=idx)
         a, r, dm = (ag._preproc_amp_obs(d[k], aidx) for k in ("amp_obs", "amp_obs_replay", "amp_obs_demo"))
@@ -61,7 +61,7 @@ if len(sys.argv) > 1 and sys.argv[1] in STAGES:
         ag.grads.zero()
         (ppo + ag._disc_coef * di["disc_loss"]).backward()
     if stage == "E_full":
-        body = ag._graph_step_body
+        body = up._step_body
     with ag.grads.shadow_scope():
         s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):

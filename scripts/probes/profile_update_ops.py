@@ -16,8 +16,8 @@ agent.train_epoch()
 agent.train_epoch()
 torch.cuda.synchronize()
 agent.set_train()
-agent._graph_static_dataset()
-body = lambda: agent._graph_step_body()
+agent._update._refresh_dataset()
+body = agent._update._step_body
 for _ in range(2):
     body()
 torch.cuda.synchronize()

@@ -25,7 +25,7 @@ def run(graph, streams=True):
     agent.init_train()
     infos = [agent.train_epoch() for _ in range(3)]
     st = agent.optimizer.state[agent.grads.flat_param]
-    return dict(graph=agent._graph is not None, three_graphs=isinstance(agent._graph, tuple), two_streams=agent._branches is not None, p0=p0, p=agent.grads.flat_param.clone(), mean=agent.running_mean_std.running_mean.clone(),
+    return dict(graph=agent.update_graphs > 0, three_graphs=agent.update_graphs == 3, two_streams=agent.update_streams == 2, p0=p0, p=agent.grads.flat_param.clone(), mean=agent.running_mean_std.running_mean.clone(),
                 var=agent._amp_input_mean_std.running_var.clone(), count=float(agent.running_mean_std.count), step=int(st["step"]),
                 info=infos[-1], expected=3 * agent.mini_epochs_num * agent.num_minibatches)
 

@@ -892,9 +892,9 @@ def test_captured_update_trains_the_other_network_and_observation_variants(over)
     for _ in range(3):
         info = agent.train_epoch()
         assert np.isfinite([info["actor_loss"], info["critic_loss"], info["disc_loss"], info["kl"]]).all(), info
-    assert agent._graph is not None and not torch.equal(p0, agent.grads.flat_param)
+    assert agent.update_graphs > 0 and not torch.equal(p0, agent.grads.flat_param)
     #  the default form: THREE linear graphs per step -- policy pass, discriminator pass captured on its own stream, tail -- not one graph
-    assert isinstance(agent._graph, tuple) and len(agent._graph) == 3 and agent._branches is not None
+    assert agent.update_graphs == 3 and agent.update_streams == 2
     st = agent.optimizer.state[agent.grads.flat_param]
     assert int(st["step"]) == 3 * agent.mini_epochs_num * agent.num_minibatches
     for p in agent.grads.params:

@@ -274,14 +274,24 @@ def test_pnn_network_and_forward_pmcp():
 def test_stale_gradient_accumulator_probe():
     """The guard in front of the update-graph capture: an autograd-tracked copy of a parameter held by the caller keeps that parameter's
     AccumulateGrad node alive (bound to the stream it was created on) and must be detected; detached snapshots are fine."""
+    from phc_amd.learning.update_graph import stale_grad_accumulators
     agent = IMAmpAgent(FakeVecEnv(32), small_cfg(), bf16=False)
-    assert not agent._stale_grad_accumulators()
+    assert not stale_grad_accumulators(agent.grads.params)
     snap = agent.model.a2c_network.mu.weight.detach().clone()
-    assert not agent._stale_grad_accumulators()
+    assert not stale_grad_accumulators(agent.grads.params)
     tracked = agent.model.a2c_network.mu.weight.clone()
-    assert agent._stale_grad_accumulators()
+    assert stale_grad_accumulators(agent.grads.params)
     del tracked
-    assert not agent._stale_grad_accumulators() and snap is not None
+    assert not stale_grad_accumulators(agent.grads.params) and snap is not None
+
+
+@pytest.mark.parametrize("key", ["debug_actor_steps", "debug_critic_steps", "debug_disc_steps", "debug_reset_at_rollout_start"])
+def test_removed_diagnostic_keys_are_rejected_by_name(key):
+    """The knobs of the finished seed study are gone: a config that still sets one fails at construction, naming the key, instead of being ignored."""
+    cfg = small_cfg()
+    cfg["learning"]["params"]["config"][key] = 24
+    with pytest.raises(ValueError, match=key):
+        IMAmpAgent(FakeVecEnv(32), cfg, bf16=False)
 
 
 def test_first_write_protocol_of_the_flat_bucket():

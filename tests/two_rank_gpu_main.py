@@ -43,7 +43,7 @@ def worker(rank, world, port, graph, q, backend="gloo", split=False):
     dist.all_gather(sg, stats)
     if rank == 0:
         q.put({"same_params": all(bool(torch.equal(gather[0], g)) for g in gather), "same_stats": all(bool(torch.allclose(sg[0], s)) for s in sg),
-               "graph": agent._graph is not None, "finite": bool(torch.isfinite(flat).all()), "actor_loss": info["actor_loss"],
+               "graph": agent.update_graphs > 0, "finite": bool(torch.isfinite(flat).all()), "actor_loss": info["actor_loss"],
                "collectives": agent.num_collectives, "expected_collectives": (2 if split else 1) * 3 * agent.mini_epochs_num * agent.num_minibatches,
                "backend": dist.get_backend(), "world": dist.get_world_size()})
     dist.destroy_process_group()
