@@ -119,6 +119,9 @@ struct AbaLane {
     int jsrc;         // body whose joint links this body to its solver parent (itself; its solver parent for a REVERSED body; -1 base)
     int bsrc;         // bodies whose own joint is solved by a reversed body: that body (their kinematic parent), else -1
     V3 r_local;       // offset from parent origin, parent frame
+    // what aba_body_init's ground contact needs BEFORE it can request anything else -- kept for the launch so that no load of a sub-step depends on
+    // another one's result: the body's mass, the broad-phase height bound f[34] and its slice of the contact-point table (start | count << 16)
+    float mass, cp_bound; int cp_range;
     // --- state ---
     Q4 q;             // joint rotation child-in-parent (root: world rotation)
     V3 wj;            // joint velocity, child frame (root: unused)
@@ -202,6 +205,8 @@ PHC_HD void aba_load_model(AbaLane& L, const phc_model_t& m, int j, bool reroot 
     L.rw = L.cw = L.ca = v3(0.f, 0.f, 0.f);
     const float* f = model_body(m, j);
     L.r_local = v3(f[0], f[1], f[2]);
+    L.mass = f[3]; L.cp_bound = f[34];
+    L.cp_range = model_tab(m, 8, j) | (model_tab(m, 9, j) << 16);
     L.arm = v3(f[19], f[20], f[21]);
     L.fself = L.nself = v3(0.f, 0.f, 0.f);
     L.cap_a = v3(f[36], f[37], f[38]); L.cap_b = v3(f[39], f[40], f[41]); L.cap_r = f[42]; L.cap_m = f[3]; L.cap_owner = j;
@@ -267,17 +272,19 @@ PHC_HD void aba_kinematics_from_parent(AbaLane& L, Q4 Qp, V3 pp, V3 wp, V3 vp) {
 // level-step needs them, and an instruction there is issued once per tree level.  (Root: zero, set by aba_fk_level.)
 // With a re-rooted solver tree the "parent" is the SOLVER parent and positions are the bodies' solver reference points (the anchor of
 // the joint towards the solver parent: a material point of both bodies, so the rigid-body relations keep their form).
-PHC_HD void aba_velocity_products(AbaLane& L, const phc_model_t& m, int j, const Xch& x, bool reroot) {
+// `offs`: a copy of every body's reference-point offset f[44..47), 3 floats per body (the kernel keeps one in LDS: the two reads then travel with the
+// slot reads below instead of being an L2 round trip of their own in every sub-step); nullptr: read from the model.
+PHC_HD void aba_velocity_products(AbaLane& L, const phc_model_t& m, int j, const Xch& x, bool reroot, const float* offs = nullptr) {
     if (L.slevel <= 0) { L.rw = L.cw = L.ca = v3(0.f, 0.f, 0.f); return; }
     constexpr int es = Xch::es;
     const float* ps = xslot(x, L.sparent);
     const V3 pp = v3(ps[10 * es], ps[11 * es], ps[12 * es]), wp = v3(ps[13 * es], ps[14 * es], ps[15 * es]);
     L.rw = L.p - pp;
     if (reroot) {   // reference points instead of origins (zero offsets for every body that is not reversed)
-        const float* f = model_body(m, j);
-        const float* fp = model_body(m, L.sparent);
-        L.rw = L.rw + quat_rotate(L.Q, v3(f[44], f[45], f[46]))
-                    - quat_rotate(q4(ps[6 * es], ps[7 * es], ps[8 * es], ps[9 * es]), v3(fp[44], fp[45], fp[46]));
+        const float* f = offs ? offs + 3 * j : model_body(m, j) + 44;
+        const float* fp = offs ? offs + 3 * L.sparent : model_body(m, L.sparent) + 44;
+        L.rw = L.rw + quat_rotate(L.Q, v3(f[0], f[1], f[2]))
+                    - quat_rotate(q4(ps[6 * es], ps[7 * es], ps[8 * es], ps[9 * es]), v3(fp[0], fp[1], fp[2]));
     }
     L.cw = cross(wp, L.w - wp);
     L.ca = cross(wp, cross(wp, L.rw));
@@ -434,10 +441,55 @@ PHC_HD void aba_ground_force_rigid(const AbaLane& L, const phc_sim_params_t& prm
     *Fout = F; *Nout = N;
 }
 
+// Which instantiations keep model constants for the launch and batch the loads of a sub-step (aba_body_init, aba_velocity_products, aba_accel_finish, the
+// lagged level-step; k_sim_step): penalty contact with spherical joints.  The rigid-contact and the revolute instantiations sit at 255-256 VGPRs, where every
+// value kept longer or load held in flight spills: they read as they always did.
+template <int JT, bool RIGID>
+PHC_HD constexpr bool aba_batched_constants() { return !RIGID && JT == PHC_JT_SPHERICAL; }
+
+// Touching points first (round 3): bit k = point k of the body's `n` (<= PHC_CP_BITS) points is below the plane.  The heights are formed from the z row of R only
+// (4 instructions per point); aba_body_init's walk then visits the SET BITS -- one iteration per touching point of the busiest lane -- instead of one dependent
+// table load and one depth test per point (the 8-corner feet made every sub-step walk 8 iterations).
+// serial: one loop over the points; the compiler keeps four loads in flight.
+PHC_HD CpMask cp_touching_serial(const M3& R, float pz, const float* cp, int n) {
+    CpMask touching = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 8
+#endif
+    for (int k = 0; k < n; ++k) {
+        const float az = R.m[6] * cp[4 * k] + R.m[7] * cp[4 * k + 1] + R.m[8] * cp[4 * k + 2];
+        if (cp[4 * k + 3] - (pz + az) > 0.f) touching |= (CpMask)1 << k;
+    }
+    return touching;
+}
+// batched: groups of eight points, their eight records requested before the first is used and no branch between them (a group's loads past the body's last
+// point re-read that point and are dropped by a select).  The first group stands outside the loop: most bodies have no more points, and a loop header would make
+// its loads wait for whatever the caller has in flight.
+PHC_HD CpMask cp_touching_batched(const M3& R, float pz, const float* cp, int n) {
+    constexpr int CG = 8;
+    CpMask touching = 0;
+    auto group = [&](int k0) {
+        float c[CG][4];
+        for (int i = 0; i < CG; ++i) {
+            const int k = k0 + i < n ? k0 + i : n - 1;
+            for (int e = 0; e < 4; ++e) c[i][e] = cp[4 * k + e];
+        }
+        for (int i = 0; i < CG; ++i) {
+            const float az = R.m[6] * c[i][0] + R.m[7] * c[i][1] + R.m[8] * c[i][2];
+            const bool t = (c[i][3] - (pz + az) > 0.f) & (k0 + i < n);
+            touching |= (CpMask)(t ? 1 : 0) << (k0 + i);
+        }
+    };
+    if (n > 0) group(0);
+    for (int k0 = CG; k0 < n; k0 += CG) group(k0);
+    return touching;
+}
+
 // ---- per-body initialisation of I^A, p^A and of the joint drive (no communication) ----
 // `new_sim_call`: first sub-step of a gym.simulate call -- the explicit `pd` torque is recomputed there (humanoid.py:1608-1616).
 // `f`: the body's PHC_BODY_FLOATS constants -- straight from the model (L2) or a register copy the caller made once per launch;
 // `cp_start / cp_total`: the body's slice of the contact-point table.
+// Penalty contact takes the mass and the broad-phase bound from the lane (aba_load_model), so the contact-point loads depend on no other load of the sub-step.
 // `RIGID` / `pass`: contact_model 1 (include/phc_amd.h) -- the sub-step is solved contact_iterations times; pass 0 decides active set and friction
 // cone on the current velocities, pass k > 0 on the end-of-step velocities the previous solve predicts (L.acc_w / L.acc_v); the joint drive is
 // formed in pass 0 only (it does not depend on the contact forces).
@@ -447,10 +499,25 @@ PHC_HD void aba_ground_force_rigid(const AbaLane& L, const phc_sim_params_t& prm
 template <int JT, bool RIGID>
 PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params_t& prm, float dt, int j, bool new_sim_call,
                           const float* f, int cp_start, int cp_total, bool reroot, int pass, bool lag = false) {
-    const float mass = f[3];
+    constexpr bool BATCH = aba_batched_constants<JT, RIGID>();
+    const float mass = BATCH ? L.mass : f[3];
     // every spatial quantity of the body is taken about its solver reference point o = p + R off (the origin unless the body is reversed)
     const SolverRef sr = model_solver_ref(f, reroot);
+    // (BATCH: the gains, effort limits and armature the drive at the end of this function needs are requested here, with the inertia: they arrive while the
+    //  contact points are worked on instead of costing a round trip of their own behind them)
+    float fd[12];
+    if (BATCH) for (int k = 0; k < 12; ++k) fd[k] = f[13 + k];
     M3 R = quat_to_mat(L.Q);
+    // ground contact, penalty model, part 1: which points touch.  BATCH: ahead of the inertia, so that the point loads are in flight together with the
+    // constants above; otherwise where it always was, behind the inertia.
+    // Broad phase: f[34] bounds |contact point| + radius, so above that height nothing of this body reaches the plane
+    const float* cp = m.floats + PHC_MAX_BODIES * PHC_BODY_FLOATS + cp_start * 4;
+    int cp_count = 0;
+    CpMask touching = 0;
+    if (BATCH) {
+        cp_count = (L.p.z < L.cp_bound) ? cp_total : 0;
+        touching = cp_touching_batched(R, L.p.z, cp, cp_count < PHC_CP_BITS ? cp_count : PHC_CP_BITS);
+    }
     Sym3 Io = rot_sym(R, sr.Io);
     V3 mc = mat_mul(R, sr.mc);
     const V3 so = mat_mul(R, sr.off);
@@ -468,25 +535,13 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
     L.pA.f = cross(L.w, cross(L.w, mc)) - g * mass;
     // ground contact: plane z = 0, normal +z
     L.fcontact = v3(0.f, 0.f, 0.f);
-    const float* cp = m.floats + PHC_MAX_BODIES * PHC_BODY_FLOATS + cp_start * 4;
     if (RIGID) {
         aba_ground_contact_rigid(L, prm, dt, R, so, f, cp, cp_total, pass);
     } else {
     const float cn = prm.contact_stiffness * dt + prm.contact_damping;
-    // broad phase: f[34] bounds |contact point| + radius, so above that height nothing of this body reaches the plane
-    const int cp_count = (L.p.z < f[34]) ? cp_total : 0;
-    // touching points first (round 3): the heights of up to 32 of the body's points above the plane are formed branch-free with their table
-    // loads in flight together (the z row of R only: 4 instructions per point); the loop below then visits the SET BITS -- one iteration per
-    // touching point of the busiest lane, each with its point's record already requested -- instead of one dependent table load and one
-    // depth test per point (the 8-corner feet made every sub-step walk 8 iterations)
-    CpMask touching = 0;
-    const int cp_fast = cp_count < PHC_CP_BITS ? cp_count : PHC_CP_BITS;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 8
-#endif
-    for (int k = 0; k < cp_fast; ++k) {
-        const float az = R.m[6] * cp[4 * k] + R.m[7] * cp[4 * k + 1] + R.m[8] * cp[4 * k + 2];
-        if (cp[4 * k + 3] - (L.p.z + az) > 0.f) touching |= (CpMask)1 << k;
+    if (!BATCH) {
+        cp_count = (L.p.z < f[34]) ? cp_total : 0;
+        touching = cp_touching_serial(R, L.p.z, cp, cp_count < PHC_CP_BITS ? cp_count : PHC_CP_BITS);
     }
     if (lag) touching &= L.c_touch;   // (a point that arrives between two fresh sub-steps joins at the next one: its impedance is not in the kept I^A)
     // one iteration per touching point of the busiest lane; the NEXT touching point's record is requested before the current one is worked on
@@ -598,13 +653,14 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
         // effort limit (gear=500): the SPRING term saturates; the damping term stays fully implicit, so a saturated
         // drive can never inject energy (a hard clamp of the total would turn the drive into a constant torque on a
         // 0.02 kg m^2 armature -> 1e4 rad/s^2)
-        const V3 kp = v3(f[13], f[14], f[15]), kd = v3(f[16], f[17], f[18]), eff = v3(f[22], f[23], f[24]);
+        const float* fg = BATCH ? fd : f + 13;   // [0..3) kp, [3..6) kd, [6..9) armature, [9..12) effort limit
+        const V3 kp = v3(fg[0], fg[1], fg[2]), kd = v3(fg[3], fg[4], fg[5]), eff = v3(fg[9], fg[10], fg[11]);
         V3 sp = v3(fminf(fmaxf(kp.x * err.x, -eff.x), eff.x), fminf(fmaxf(kp.y * err.y, -eff.y), eff.y), fminf(fmaxf(kp.z * err.z, -eff.z), eff.z));
         V3 tau = v3(sp.x - (kd.x + dt * kp.x) * L.wj.x, sp.y - (kd.y + dt * kp.y) * L.wj.y, sp.z - (kd.z + dt * kp.z) * L.wj.z);
         V3 d = v3(dt * kd.x + dt * dt * kp.x, dt * kd.y + dt * dt * kp.y, dt * kd.z + dt * dt * kp.z);
         L.tau_local = tau;
         L.dimp = d;
-        const V3 dd = d + v3(f[19], f[20], f[21]);   // + armature (read here: not pinned in registers across the sweeps)
+        const V3 dd = d + v3(fg[6], fg[7], fg[8]);   // + armature (read here: not pinned in registers across the sweeps)
         if (dd.x == dd.y && dd.y == dd.z) { L.diso = dd.x; }
         else { L.diso = -1.f; if (!lag) L.Dw = rot_diag(R, dd); }
         L.tau_w = mat_mul(R, tau);
@@ -765,18 +821,24 @@ PHC_HD bool aba_collide_pair(const phc_sim_params_t& prm, float dt, int i, int k
     return b == 0 ? aba_pair_narrow(prm, dt, i, k, x, caps) : b == 2;
 }
 // lane `l` of `nl` lanes of the env's group: its share of the candidate pairs, dealt round-robin, kept in LDS as [pair slot t][thread]
-// (round 3; 18 x 32 lanes hold the 245 pairs of the SMPL humanoid, 18 x 64 the 589 of G1)
+// (round 3; 18 x 32 lanes hold the 245 pairs of the SMPL humanoid, 18 x 64 the 589 of G1).  The NP table words of a lane are independent: they are
+// requested together and waited for once (written with a branch around each load they were NP dependent L2 round trips in the prologue).
 #define PHC_SC_MAX_PER_LANE 18
 template <int NP>
 PHC_HD void aba_load_pairs(int* pr /*[NP][stride]*/, int stride, const phc_model_t& m, int l, int nl) {
     const int np = model_num_pairs(m);
+    int v[NP];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-    for (int t = 0; t < NP; ++t) {
+    for (int t = 0; t < NP; ++t) {   // every load unconditional (a slot past the list reads the count word in front of it) and -1 selected afterwards: NP loads in flight, one wait
         const int q = t * nl + l;
-        pr[t * stride] = q < np ? model_pair(m, q) : -1;
+        v[t] = m.ints[4 + PHC_NTAB * PHC_MAX_BODIES + (q < np ? 1 + q : 0)];
     }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int t = 0; t < NP; ++t) pr[t * stride] = t * nl + l < np ? v[t] : -1;
 }
 // Temporal coherence over the sub-steps of ONE launch (round 2): the first sub-step tests every candidate pair and remembers in `near`
 // (bit t = pair t of this lane) the ones whose surfaces are closer than PHC_SC_SKIP_MARGIN = 0.12 m; the remaining sub-steps (3 x 1/120 s)
@@ -842,6 +904,28 @@ PHC_HD void shift_to_parent(const Inertia6& I, const Force6& p, V3 r, float* out
     out[21 * es] = n.x; out[22 * es] = n.y; out[23 * es] = n.z; out[24 * es] = p.f.x; out[25 * es] = p.f.y; out[26 * es] = p.f.z;
 }
 
+// The 6-float force hand-over of the bias-only (lagged) level-step lives at floats [20..26) of the slot: 16-byte aligned (the slot stride is 7 x 16 bytes and the
+// kernel aligns the exchange area), so one 128-bit and one 64-bit LDS access move it.  Free at that time: the drive terms [19..28) were fetched before the
+// sweep, the accelerations sweep writes [19..22) after it.  (The fresh level-step hands over all 27 floats at [0..27).)
+#define PHC_XCH_LAG 20
+PHC_HD void xch_read6(const float* s, float* o) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float4 a = *reinterpret_cast<const float4*>(s);
+    const float2 b = *reinterpret_cast<const float2*>(s + 4);
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y;
+#else
+    for (int k = 0; k < 6; ++k) o[k] = s[k];
+#endif
+}
+PHC_HD void xch_write6(float* s, const float* o) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *reinterpret_cast<float4*>(s) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float2*>(s + 4) = make_float2(o[4], o[5]);
+#else
+    for (int k = 0; k < 6; ++k) s[k] = o[k];
+#endif
+}
+
 PHC_HD void accumulate_child(Inertia6& I, Force6& p, const float* s, int es) {
     I.A.xx += s[0 * es]; I.A.xy += s[1 * es]; I.A.xz += s[2 * es]; I.A.yy += s[3 * es]; I.A.yz += s[4 * es]; I.A.zz += s[5 * es];
     for (int k = 0; k < 9; ++k) I.B[k] += s[(6 + k) * es];
@@ -861,12 +945,23 @@ template <int JT>
 PHC_HD void aba_backward_level(AbaLane& L, int level, int j, const Xch& x, bool lag = false) {
     if (L.slevel != level) return;
     if (lag) {
-        constexpr int es = Xch::es;
-        for (int k = 0; k < 3; ++k)
-            if (k < L.nchild) {
-                const float* s = xslot(x, L.child[k]);
-                L.pA.n.x += s[21 * es]; L.pA.n.y += s[22 * es]; L.pA.n.z += s[23 * es]; L.pA.f.x += s[24 * es]; L.pA.f.y += s[25 * es]; L.pA.f.z += s[26 * es];
-            }
+        // Batched (NB = 3, spherical joints): every child's hand-over is requested before the first one is added.  A missing child reads the body's own slot
+        // (valid memory, any content) and is dropped by the select below, so the sums keep the child order 0, 1, 2 and a level-step waits for LDS once
+        // instead of once per child and vector half.
+        // One by one (NB = 1, the revolute instantiations: at the register limit they cannot hold 18 floats in flight): child 0 is read as above; child
+        // k > 0 is read right before it is added, and the loop ends at the first missing child -- so for k > 0 the select below always takes the sum and
+        // h[k] is never used unread.
+        // (One body for both, and selects rather than branches, on purpose: measured against two plain loops -- `if (k < nchild)` per child for NB = 1, add
+        // and undo for NB = 3 -- this form is 1.2 us faster on the SMPL launch and 1.6 us on G1's, profiles/stepper_chain_latency/README.md.)
+        constexpr int NB = aba_batched_constants<JT, false>() ? 3 : 1;   // children requested together
+        float h[3][6];
+        for (int k = 0; k < NB; ++k) xch_read6(xslot(x, k < L.nchild ? L.child[k] : j) + PHC_XCH_LAG, h[k]);
+        for (int k = 0; k < 3; ++k) {
+            const bool on = k < L.nchild;
+            if (NB == 1 && k > 0) { if (!on) break; xch_read6(xslot(x, L.child[k]) + PHC_XCH_LAG, h[k]); }
+            L.pA.n.x = on ? L.pA.n.x + h[k][0] : L.pA.n.x; L.pA.n.y = on ? L.pA.n.y + h[k][1] : L.pA.n.y; L.pA.n.z = on ? L.pA.n.z + h[k][2] : L.pA.n.z;
+            L.pA.f.x = on ? L.pA.f.x + h[k][3] : L.pA.f.x; L.pA.f.y = on ? L.pA.f.y + h[k][4] : L.pA.f.y; L.pA.f.z = on ? L.pA.f.z + h[k][5] : L.pA.f.z;
+        }
         if (level == 0) return;
         L.u = L.tau_w - L.pA.n;
         const V3 t = sym_mul(L.IA.A, L.cw) + B_mul(L.IA.B, L.ca);
@@ -874,8 +969,8 @@ PHC_HD void aba_backward_level(AbaLane& L, int level, int j, const Xch& x, bool 
         const V3 z = sym_mul(L.Di, L.u - t);
         const V3 f = L.pA.f + sb + Bt_mul(L.IA.B, z);
         const V3 n = L.pA.n + t + sym_mul(L.IA.A, z) + cross(L.rw, f);
-        float* o = xslot(x, j);
-        o[21 * es] = n.x; o[22 * es] = n.y; o[23 * es] = n.z; o[24 * es] = f.x; o[25 * es] = f.y; o[26 * es] = f.z;
+        const float o[6] = {n.x, n.y, n.z, f.x, f.y, f.z};
+        xch_write6(xslot(x, j) + PHC_XCH_LAG, o);
         return;
     }
     for (int k = 0; k < 3; ++k)
@@ -1006,7 +1101,7 @@ PHC_HD void aba_fetch_drive(AbaLane& L, int j, const Xch& x) {
 // After the acceleration sweep: what aba_integrate_joint reads from L.u / L.ca.  A joint solved by a reversed body gets that body's
 // relative acceleration with the opposite sign (beta_c = alpha_c - alpha_p - w_p x w_c = -(alpha_p - alpha_c - w_c x w_p)); the
 // simulator's root, when it is not the solver base, gets its own alpha and the acceleration of its ORIGIN from that of its reference point.
-PHC_HD void aba_accel_finish(AbaLane& L, const phc_model_t& m, int j, const Xch& x) {
+PHC_HD void aba_accel_finish(AbaLane& L, const phc_model_t& m, int j, const Xch& x, const float* offs = nullptr /*as in aba_velocity_products*/) {
     if (L.level < 0) return;
     constexpr int es = Xch::es;
     if (L.bsrc >= 0) {
@@ -1015,9 +1110,9 @@ PHC_HD void aba_accel_finish(AbaLane& L, const phc_model_t& m, int j, const Xch&
     }
     if (L.level == 0 && L.slevel > 0) {
         const float* s = xslot(x, j);
-        const float* f = model_body(m, j);
+        const float* f = offs ? offs + 3 * j : model_body(m, j) + 44;
         const V3 alpha = v3(s[0 * es], s[1 * es], s[2 * es]), a = v3(s[3 * es], s[4 * es], s[5 * es]);
-        const V3 d = -quat_rotate(L.Q, v3(f[44], f[45], f[46]));   // origin minus reference point
+        const V3 d = -quat_rotate(L.Q, v3(f[0], f[1], f[2]));   // origin minus reference point
         L.u = alpha;
         L.ca = a + cross(alpha, d) + cross(L.w, cross(L.w, d));
     }

@@ -9,6 +9,7 @@
 //     tolerances (tests/test_dynamics.py) hold with these approximations.  The task kernels, which ARE pinned to the
 //     reference at 1e-5 and rely on IEEE NaN/division semantics, are NOT compiled this way.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "phc_aba.h"
 
 using namespace phc;
@@ -64,26 +65,42 @@ extern "C" int32_t phc_debug_timeline(unsigned long long* out512, int32_t block)
 
 // A2: pd_tar = offset + scale * action (humanoid.py:1711-1713); env.res_action (sim.pd_ref set): reference joint position + scale * action,
 // kept within pi / 2 of the current joint position (humanoid_im.py:1094-1099); frozen DoFs -> 0 (humanoid.py:1549-1554)
-__device__ __forceinline__ float pd_target_of(const phc_sim_state_t& sim, const float* __restrict__ actions, const float* __restrict__ pd_off,
-                                              const float* __restrict__ pd_scale, const int32_t* __restrict__ freeze, int64_t env, int nd, int d) {
-    const float sa = __fmul_rn(pd_scale[d], actions[env * nd + d]);
-    float t;
-    if (sim.pd_ref != nullptr) {
-        const float q = sim.dof_state[(env * nd + d) * 2];
-        const float half_pi = 1.57079637f;   // float32(np.pi / 2)
-        t = fmaxf(fminf(__fadd_rn(sim.pd_ref[env * nd + d], sa), __fadd_rn(q, half_pi)), __fsub_rn(q, half_pi));
-    } else {
-        t = __fadd_rn(pd_off[d], sa);
+// The K DoFs of one joint at once: every input of the K targets -- scale, action, offset or reference position, joint position, freeze flag -- is
+// requested before the first target is formed, through pointers that are valid in every mode (no branch between the loads; what a mode does not use
+// is dropped by a select), so the prologue waits for them once instead of 2-4 times per DoF.
+template <int K>
+__device__ __forceinline__ void pd_targets_of(const phc_sim_state_t& sim, const float* __restrict__ actions, const float* __restrict__ pd_off,
+                                              const float* __restrict__ pd_scale, const int32_t* __restrict__ freeze, const int32_t* valid_ints,
+                                              int64_t env, int nd, int d0, float* tg) {
+    const bool ref = sim.pd_ref != nullptr, frz = freeze != nullptr;
+    const int64_t i0 = env * nd + d0;
+    const float* basep = ref ? sim.pd_ref + i0 : pd_off + d0;
+    const int32_t* frzp = frz ? freeze + d0 : valid_ints;
+    float sc[K], ac[K], base[K], q[K];
+    int32_t fz[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        sc[k] = pd_scale[d0 + k]; ac[k] = actions[i0 + k]; base[k] = basep[k];
+        q[k] = sim.dof_state[(i0 + k) * 2];   // (the state load requested it already)
+        fz[k] = frzp[k];
     }
-    if (freeze != nullptr && freeze[d]) t = 0.f;
-    return t;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float sa = __fmul_rn(sc[k], ac[k]);
+        asm("" : "+v"(sa));   // the product is rounded on its own: this file's -ffast-math would otherwise contract it with the add below into one fma
+        const float half_pi = 1.57079637f;   // float32(np.pi / 2)
+        const float t0 = __fadd_rn(base[k], sa);
+        const float t = ref ? fmaxf(fminf(t0, __fadd_rn(q[k], half_pi)), __fsub_rn(q[k], half_pi)) : t0;
+        tg[k] = (frz && fz[k]) ? 0.f : t;
+    }
 }
 
 
 // ------------------------------------------------------------------------------------------
 // Staged epilogue.  A lane would otherwise issue ~50 scattered 4-byte global stores, all wavefronts at the same instant.  The output slices of the E consecutive envs of ONE wavefront are contiguous and 16-byte aligned in every
 // simulator tensor (E * 13, E * NB * 13, E * ND * 2, ... floats), so the lanes first write their values into the (now idle) LDS
-// exchange area in exactly that layout and the wavefront then streams each slice out with coalesced dwordx4 / dwordx2 stores.
+// exchange area in exactly that layout and the wavefront then streams each slice out with coalesced dwordx4 / dwordx2 stores, four LDS reads
+// in flight per wait (stage_copy_out).
 // ------------------------------------------------------------------------------------------
 struct StageLayout { int root, dof, force, contact, rbs, total; };
 __device__ __forceinline__ StageLayout stage_layout(int E, int nb, int nd, bool with_force, bool with_contact) {
@@ -108,11 +125,17 @@ __device__ __forceinline__ phc_sim_state_t stage_state(const phc_sim_state_t& si
 }
 template <int W>
 __device__ __forceinline__ void stage_copy_out(float* __restrict__ dst, const float* __restrict__ src, int n, int tid, int nthreads) {
-    if (W == 4) {
-        for (int i = tid; i < n / 4; i += nthreads) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
-    } else {
-        for (int i = tid; i < n / 2; i += nthreads) reinterpret_cast<float2*>(dst)[i] = reinterpret_cast<const float2*>(src)[i];
+    // four independent LDS reads per wait, then their four stores (one read per iteration cost the wavefront one LDS latency per 512 bytes streamed out)
+    typedef typename std::conditional<W == 4, float4, float2>::type T;
+    const int m = n / W;
+    const T* s = reinterpret_cast<const T*>(src);
+    T* d = reinterpret_cast<T*>(dst);
+    int i = tid;
+    for (; i + 3 * nthreads < m; i += 4 * nthreads) {
+        const T a = s[i], b = s[i + nthreads], c = s[i + 2 * nthreads], e = s[i + 3 * nthreads];
+        d[i] = a; d[i + nthreads] = b; d[i + 2 * nthreads] = c; d[i + 3 * nthreads] = e;
     }
+    for (; i < m; i += nthreads) d[i] = s[i];
 }
 // all lanes of the wavefront: stream the staged slices of envs [env0, env0 + E) to the simulator tensors
 template <int E>
@@ -155,10 +178,14 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
                                                 const float* __restrict__ actions, const float* __restrict__ pd_off,
                                                 const float* __restrict__ pd_scale, const int32_t* __restrict__ freeze,
                                                 int num_sim_calls, const int64_t* __restrict__ env_ids, int num_listed) {
-    __shared__ float xch_all[64 * PHC_XCH_STRIDE];   // one exchange slot per lane == body
+    __shared__ __attribute__((aligned(16))) float xch_all[64 * PHC_XCH_STRIDE];   // one exchange slot per lane == body (16-byte aligned: the lagged hand-over moves as b128 + b64)
     __shared__ float cap_all[64 * PHC_CAP_STRIDE];
     __shared__ int pair_all[PHC_SC_MAX_PER_LANE * 64];   // candidate pairs of body-body contact: [pair slot][thread]
     __shared__ float favg_all[STEP ? 64 * 6 : 1];        // force_average: per-lane sums of S4 / S5 over the sub-steps
+    // every body's solver-reference offset f[44..47): read in every sub-step by the body and its solver children.  (The rigid-contact and the revolute
+    // instantiations sit at the register limit -- the table's address is one more live value -- and keep reading the model.)
+    constexpr bool BATCH = STEP && aba_batched_constants<JT, RIGID>();   // (phc_aba.h)
+    __shared__ float off_all[BATCH ? 64 * 3 : 1];
     const int lane = threadIdx.x & (GRP - 1);
     const int grp = threadIdx.x / GRP;
     const int64_t slot = (int64_t)blockIdx.x * (64 / GRP) + grp;
@@ -181,17 +208,17 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     if (active) {
         aba_load_model(L, model, body);
         if (JT == PHC_JT_REVOLUTE) aba_load_model_rev(L, model, body);
+        if (BATCH) { const float* f = model_body(model, body); float* o = off_all + grp * GRP * 3 + body * 3; o[0] = f[44]; o[1] = f[45]; o[2] = f[46]; }   // (read behind the barriers of the kinematics below)
         // (the state is requested BEFORE the new PD targets are stored: no load of this prologue has to wait behind a store, and the targets go
         //  into the lane's registers directly instead of through memory)
         const bool new_targets = STEP && actions != nullptr && body >= 1;
         aba_load_state<JT>(L, sim, nd, env, body, !new_targets);
         if (new_targets) {
+            constexpr int K = JT == PHC_JT_REVOLUTE ? 1 : 3;
             float tg[3] = {0.f, 0.f, 0.f};
-            for (int k = 0; k < (JT == PHC_JT_REVOLUTE ? 1 : 3); ++k) {
-                const int d = L.dof_start + k;
-                tg[k] = pd_target_of(sim, actions, pd_off, pd_scale, freeze, env, nd, d);
-                sim.pd_target[env * nd + d] = tg[k];
-            }
+            pd_targets_of<K>(sim, actions, pd_off, pd_scale, freeze, model.ints, env, nd, L.dof_start, tg);
+#pragma unroll
+            for (int k = 0; k < K; ++k) sim.pd_target[env * nd + L.dof_start + k] = tg[k];   // (stored after all K are formed: no load waits behind a store)
             L.target = v3(tg[0], tg[1], tg[2]);
         }
     }
@@ -215,6 +242,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
         const float dt = prm.sim_dt / (float)prm.substeps;
         const int nsub = num_sim_calls * prm.substeps;
         float* caps = cap_all + grp * GRP * PHC_CAP_STRIDE;
+        const float* offs = BATCH ? off_all + grp * GRP * 3 : nullptr;
         uint32_t near_pairs = 0;
         if (prm.self_collision) aba_load_pairs<PHC_SC_MAX_PER_LANE>(pair_all + threadIdx.x, 64, model, lane, GRP);
         // the backward / acceleration sweeps walk the solver tree (model.py solver_tree(): re-rooted where that makes it shallower)
@@ -233,7 +261,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             }
             PHC_PROF(1)
             PHC_TL(2)
-            if (active && !PHC_SKIP(1)) aba_velocity_products(L, model, body, x, true);
+            if (active && !PHC_SKIP(1)) aba_velocity_products(L, model, body, x, true, offs);
             // contact_model 1 (rigid): the sub-step's solve is repeated contact_iterations times, each pass with the active set and friction cone the
             // previous one implies (phc_aba.h aba_ground_contact_rigid); the penalty model is the single pass it always was
             const int passes = RIGID ? (prm.contact_iterations < 1 ? 1 : prm.contact_iterations) : 1;
@@ -242,7 +270,11 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             const bool lag = LAG && !RIGID && (s % prm.substeps) != 0;
             for (int pass = 0; pass < passes; ++pass) {
             PHC_TL(3)
-            if (active && !PHC_SKIP(1)) aba_body_init<JT, RIGID>(L, model, prm, dt, body, s % prm.substeps == 0, true, pass, lag);
+            // (penalty contact: the body's slice of the contact-point table from the lane's registers, not from two table loads the point loads would wait for)
+            if (active && !PHC_SKIP(1)) {
+                if (!BATCH) aba_body_init<JT, RIGID>(L, model, prm, dt, body, s % prm.substeps == 0, true, pass, lag);
+                else aba_body_init<JT, RIGID>(L, model, prm, dt, body, s % prm.substeps == 0, model_body(model, body), L.cp_range & 0xffff, L.cp_range >> 16, true, pass, lag);
+            }
             if (active && PHC_SKIP(9)) aba_body_init<JT, RIGID>(L, model, prm, dt, body, s % prm.substeps == 0, true, pass, lag);   // (profiling builds: the phase a second time, loads warm -- its pure instruction cost)
             PHC_PROF(2)
             PHC_TL(4)
@@ -261,7 +293,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             }
             }
             if (RIGID && active && (s == nsub - 1 || prm.force_average)) aba_publish_contact_rigid(L, model, prm, sim, dt, env, body, true);   // S4 / S6 from the final solve
-            if (JT == PHC_JT_SPHERICAL && rerooted && !PHC_SKIP(4)) aba_accel_finish(L, model, body, x);
+            if (JT == PHC_JT_SPHERICAL && rerooted && !PHC_SKIP(4)) aba_accel_finish(L, model, body, x, offs);
             PHC_PROF(5)
             PHC_TL(6)
             if (!PHC_SKIP(5)) aba_integrate_joint<JT>(L, prm, dt);
