@@ -579,6 +579,50 @@ typedef struct {
 int32_t phc_render(const phc_render_scene_t* scene /* host */, const phc_camera_t* cameras /* host, [views] */, int32_t views, int32_t width,
                    int32_t height, uint8_t* rgba, float* depth, int32_t* hit_id, void* stream);
 
+/* Evaluation sweep: tracking metrics accumulated on the device (csrc/phc_eval.hip; an addition to ABI 37, which stays 37).  One launch per env
+ * step of a sweep batch replaces the host path's second reference lookup, its two [N, NB, 3] device-to-host copies and the numpy metric pass of
+ * learning/im_eval.py (compute_metrics_per_clip).  One lane per body, 32-lane groups up to 32 bodies (64 above), 256-thread blocks.  Per env i:
+ *   gt_j   = position of body j of clip motion_ids[i] at t = progress_buf[i] * dt + motion_start_times[i] + motion_start_times_offset[i], plus
+ *            global_offset[i]: bit-equal to phc_motion_state's rg_pos (same loads, same blend); written to gt_out when that is given;
+ *   pred_j = position of body j in rigid_body_state.  Only the NB simulated bodies take part (no extended reference bodies);
+ *   mpjpe_step[i] = mean_j |pred_j - gt_j| (metres), every launch;
+ *   while step < clip_steps[i] - 1 (the frames the host path counts; a termination or a reset in mid-batch does not stop it):
+ *     count[i] += 1 and sums[i][0..4] += sum_j of, in this order,
+ *       |pred_j - gt_j|; the same after subtracting body root_idx from both; the same after the similarity alignment (centre both, proper rotation
+ *       with the det sign fix, scale (s1 + s2 + d s3) / sum |p|^2) of the root-relative pred onto the root-relative gt;
+ *       the second difference in time of (pred_j - gt_j) (from the third counted frame on); its first difference (from the second on).
+ *     Nothing is divided: metric = sums / (frames * NB) with frames = n, n, n, n - 2, n - 1 for count n.
+ *   failed[i] |= terminate_buf[i] != 0 && step <= clip_steps[i] - 1   (a termination after the clip's last frame is not a failure);
+ *   status[0] = number of envs with failed == 0 after this launch; status[1] = max clip_steps[i] over those of them with i < bound (0: none).
+ *     The entry point clears status on `stream` before the kernel; blocks reduce in LDS and add one integer atomic per word.
+ * `step` counts the launches of a batch from 0.  history holds the two previous frames (ring slot = step & 1), so the launches of one batch must
+ * run in order on one stream; all state is the caller's (zeroed at the start of a batch), nothing is kept in the library.
+ * PHC_EINVAL: a null lib / args / required pointer, num_envs < 0, num_bodies outside [1, PHC_MAX_BODIES] or != lib->num_bodies, root_idx outside
+ * [0, num_bodies), step < 0, bound outside [0, num_envs]. */
+typedef struct {
+    int32_t num_envs, num_bodies;             /* N, NB */
+    int32_t root_idx;
+    int32_t step;                             /* index of this launch within the batch, from 0 */
+    int32_t bound;                            /* status[1] only looks at envs below it */
+    float dt;                                 /* env step, seconds */
+    const float* rigid_body_state;            /* [N, NB, 13] */
+    const int64_t* progress_buf;              /* [N] */
+    const int64_t* terminate_buf;             /* [N] */
+    const int64_t* motion_ids;                /* [N]; nullable = the env's own index */
+    const float* motion_start_times;          /* [N] */
+    const float* motion_start_times_offset;   /* [N] */
+    const float* global_offset;               /* [N, 3] */
+    const int32_t* clip_steps;                /* [N] env steps of the env's clip */
+    float* history;                           /* [N, 2 slots, 2 (pred, gt), NB, 3] */
+    double* sums;                             /* [N, 5] */
+    int32_t* count;                           /* [N] */
+    int32_t* failed;                          /* [N] */
+    int32_t* status;                          /* [2] */
+    float* mpjpe_step;                        /* [N] */
+    float* gt_out;                            /* [N, NB, 3]; nullable */
+} phc_eval_args_t;
+int32_t phc_eval_accumulate(const phc_motion_lib_t* lib, const phc_eval_args_t* args /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

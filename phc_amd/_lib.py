@@ -105,6 +105,13 @@ class RenderScene(C.Structure):
                 ("sky_color", c_f * 3), ("light_dir", c_f * 3), ("ambient", c_f), ("diffuse", c_f)]
 
 
+class EvalArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("root_idx", c_i32), ("step", c_i32), ("bound", c_i32), ("dt", c_f),
+                ("rigid_body_state", c_p), ("progress_buf", c_p), ("terminate_buf", c_p), ("motion_ids", c_p), ("motion_start_times", c_p),
+                ("motion_start_times_offset", c_p), ("global_offset", c_p), ("clip_steps", c_p), ("history", c_p), ("sums", c_p), ("count", c_p),
+                ("failed", c_p), ("status", c_p), ("mpjpe_step", c_p), ("gt_out", c_p)]
+
+
 P = C.POINTER
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
@@ -147,6 +154,7 @@ _SIGNATURES = {
     "phc_ppo_loss_workspace": ([], c_i64),
     "phc_ppo_loss": ([c_p, c_p, c_i32] + [c_p] * 9 + [c_i64, c_i32, P(PpoParams), c_p, c_p, c_p, c_p, c_p], c_i32),
     "phc_render": ([P(RenderScene), P(Camera), c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p], c_i32),
+    "phc_eval_accumulate": ([P(MotionLib), P(EvalArgs), c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -8,31 +8,9 @@
 #include <stdlib.h>
 #include "phc_aba.h"  // model table accessors (k_fk)
 #include "phc_im.h"
+#include "phc_group.h"  // group_sum / group_or
 
 using namespace phc;
-
-// Sum / or over the G lanes of an env's group, result in every lane.  Inside a row of 16 lanes the butterfly runs on DPP operands (quad_perm xor 1,
-// xor 2, row_half_mirror, row_mirror: folded into the add, ~4 cycles each); only the steps across rows are ds_bpermute round trips (~64 cycles
-// each, round 3: seven sums x five dependent permutes were 1.8 k cycles of the post-physics wavefront's 38 k).
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-    v += __int_as_float(dpp_i<0xB1>(__float_as_int(v)));    // quad_perm:[1,0,3,2]
-    v += __int_as_float(dpp_i<0x4E>(__float_as_int(v)));    // quad_perm:[2,3,0,1]
-    v += __int_as_float(dpp_i<0x141>(__float_as_int(v)));   // row_half_mirror
-    v += __int_as_float(dpp_i<0x140>(__float_as_int(v)));   // row_mirror
-#pragma unroll
-    for (int m = 16; m < G; m <<= 1) v += __shfl_xor(v, m, G);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ int group_or(int v) {
-    v |= dpp_i<0xB1>(v); v |= dpp_i<0x4E>(v); v |= dpp_i<0x141>(v); v |= dpp_i<0x140>(v);
-#pragma unroll
-    for (int m = 16; m < G; m <<= 1) v |= __shfl_xor(v, m, G);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------
 // post_physics_step of the imitation task.  blockDim = 256 (8 envs).

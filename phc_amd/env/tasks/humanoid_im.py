@@ -375,6 +375,7 @@ class HumanoidIm:
         self.progress_buf = torch.zeros(N, **i64)
         self.randomize_buf = torch.zeros(N, **i64)
         self.extras = {}
+        self._eval_acc = None   # state of an open device metric accumulation (begin_eval_accumulation)
         self.viewer = None
         self.paused = False
 
@@ -855,12 +856,61 @@ class HumanoidIm:
                                               _stream()), "phc_im_post_physics")
         self._obs_noise()
         self._post_physics_host(new_head)
-        if flags.im_eval:  # humanoid_im.py:674-680
+        if self._eval_acc is not None:   # evaluation sweep with eval_metrics=device: one launch instead of the lookup, the copies and the host metrics
+            self._eval_accumulate()
+        elif flags.im_eval:  # humanoid_im.py:674-680
             t = self.progress_buf * self.dt + self._motion_start_times + self._motion_start_times_offset
             res = self._motion_lib.get_motion_state(self._sampled_motion_ids, t, self._global_offset)
             self.extras["mpjpe"] = (self._rigid_body_pos - res["rg_pos"]).norm(dim=-1).mean(dim=-1)
             self.extras["body_pos"] = self._rigid_body_pos.cpu().numpy()
             self.extras["body_pos_gt"] = res["rg_pos"].cpu().numpy()
+
+    # ------------------------------------------------------------------ evaluation sweep: metrics accumulated on the device (learning/im_eval.py)
+    def begin_eval_accumulation(self, clip_steps, bound):
+        """Open the device metric accumulation of one sweep batch (`eval_metrics=device`): until `end_eval_accumulation()` every
+        `post_physics_step` launches `phc_eval_accumulate` (include/phc_amd.h) in place of the host path's reference lookup and copies.
+        `clip_steps` int [N]: env steps of each env's clip; `bound`: `eval_status()`'s maximum only looks at envs below it."""
+        N, NB, dev = self.num_envs, self.num_bodies, self.device
+        if not 0 <= int(bound) <= N:
+            raise ValueError(f"bound must be in [0, {N}], not {bound}")
+        z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+        acc = dict(step=0, clip_steps=clip_steps.to(device=dev, dtype=torch.int32).contiguous(), history=z((N, 2, 2, NB, 3), torch.float32),
+                   sums=z((N, 5), torch.float64), count=z(N, torch.int32), failed=z(N, torch.int32), status=z(2, torch.int32),
+                   mpjpe=z(N, torch.float32), status_host=torch.zeros(2, dtype=torch.int32).pin_memory(), event=torch.cuda.Event())
+        assert acc["clip_steps"].shape == (N,)
+        a = L.EvalArgs()
+        a.num_envs, a.num_bodies, a.root_idx, a.bound, a.dt = N, NB, 0, int(bound), float(np.float32(self.dt))
+        a.rigid_body_state, a.progress_buf, a.terminate_buf = abi.ptr(self._rigid_body_state), abi.ptr(self.progress_buf), abi.ptr(self._terminate_buf)
+        a.motion_ids, a.global_offset = abi.ptr(self._sampled_motion_ids), abi.ptr(self._global_offset)
+        a.motion_start_times, a.motion_start_times_offset = abi.ptr(self._motion_start_times), abi.ptr(self._motion_start_times_offset)
+        for k in ("clip_steps", "history", "sums", "count", "failed", "status"):
+            setattr(a, k, abi.ptr(acc[k]))
+        a.mpjpe_step = abi.ptr(acc["mpjpe"])
+        acc["args"] = a
+        for k in ("body_pos", "body_pos_gt"):   # (a host-path sweep before this one left its last arrays in the info dict)
+            self.extras.pop(k, None)
+        self._eval_acc = acc
+
+    def _eval_accumulate(self):
+        acc = self._eval_acc
+        acc["args"].step = acc["step"]
+        L.check(self._lib.phc_eval_accumulate(self._motion_lib.struct, acc["args"], _stream()), "phc_eval_accumulate")
+        acc["step"] += 1
+        self.extras["mpjpe"] = acc["mpjpe"]   # the launch's own output buffer: the next step overwrites it (the host path hands out a fresh tensor)
+
+    def eval_status(self):
+        """(envs that have not failed, the largest clip_steps among those of them below `bound` -- 0 if none) after the last step: one 8-byte copy
+        into pinned memory and one event wait, the only synchronisation a device-metrics sweep step makes."""
+        acc = self._eval_acc
+        acc["status_host"].copy_(acc["status"], non_blocking=True)
+        acc["event"].record()
+        acc["event"].synchronize()
+        return int(acc["status_host"][0]), int(acc["status_host"][1])
+
+    def end_eval_accumulation(self):
+        """Close the accumulation; -> the device tensors (failed int32 [N], sums fp64 [N, 5], count int32 [N]), or None if none was open."""
+        acc, self._eval_acc = self._eval_acc, None
+        return None if acc is None else (acc["failed"], acc["sums"], acc["count"])
 
     def _post_physics_host(self, new_head):
         """The HOST side of a post-physics step (no launch): the AMP window moved, a reset list is pending, the info dict.  A replayed hipGraph of a

@@ -55,13 +55,99 @@ def compute_metrics_lite(pred_pos_all, gt_pos_all, root_idx=0):
     return {k: v[~np.isnan(v)].tolist() for k, v in compute_metrics_per_clip(pred_pos_all, gt_pos_all, root_idx).items()}
 
 
+def metrics_from_sums(sums, count, num_bodies):
+    """`compute_metrics_per_clip` from phc_eval_accumulate's totals: sums float64 [C, 5] (summed over frames and bodies, metres, in the order of
+    METRICS) and the counted frames [C] -> {metric: mm [C]}, NaN where a clip has no frame (fewer than three for the two differences)."""
+    n = np.asarray(count, dtype=np.float64)
+    m = {}
+    for c, k in enumerate(METRICS):
+        diff = {"accel_dist": 2, "vel_dist": 1}.get(k, 0)   # a second / first difference in time has that many frames fewer
+        ok = n >= (3 if diff else 1)
+        m[k] = np.where(ok, sums[:, c] / (np.where(ok, n - diff, 1.0) * num_bodies) * 1000, np.nan)
+    return m
+
+
+def _run_batch_host(agent, num_steps, own):
+    """One batch of the sweep with the metrics formed on the host: every step's body positions are copied back and kept until the batch ends.
+    -> (failed flags of the batch's `own` clips, {metric: per-clip values, NaN where a clip is too short})."""
+    task, env = agent.task, agent.vec_env
+    lib, N = task._motion_lib, task.num_envs
+    U = lib._num_unique_motions
+    terminate_state = torch.zeros(N, device=task.device, dtype=torch.bool)
+    preds, gts = [], []
+    obs = env.reset()
+    curr = 0
+    while True:
+        res = agent.get_action_values(obs)
+        obs, r, done, info = env.step(agent.preprocess_actions(res["mus"]))  # deterministic policy (is_determenistic=True)
+        # a termination after the clip's last frame is not a failure (im_amp.py:248)
+        term = torch.logical_and(torch.as_tensor(curr <= num_steps - 1, device=task.device), info["terminate"].bool())
+        terminate_state |= term
+        # how long this batch runs (im_amp.py:251-268): until the longest clip still alive has ended -- in the LAST batch, whose
+        # envs past the library's final clip hold wrapped-around duplicates, only the envs up to that final clip count
+        alive = (~terminate_state).cpu().numpy()
+        if alive.any():
+            last = np.flatnonzero(lib._curr_motion_ids.cpu().numpy() == U - 1)
+            if len(last):
+                bound = int(last[0]) + 1
+                curr_max = num_steps[:bound][alive[:bound]].max() if alive[:bound].any() else curr - 1
+            else:
+                curr_max = num_steps[alive].max()
+            if curr >= curr_max:
+                curr_max = curr + 1
+        else:
+            curr_max = num_steps.max()
+        preds.append(info["body_pos"])
+        gts.append(info["body_pos_gt"])
+        curr += 1
+        if curr >= curr_max or not alive.any():
+            break
+    P, G = np.stack(preds), np.stack(gts)
+    frames = [max(min(int(num_steps[i]) - 1, P.shape[0]), 0) for i in range(own)]
+    m = compute_metrics_per_clip([P[:n, i] for i, n in enumerate(frames)], [G[:n, i] for i, n in enumerate(frames)])
+    return terminate_state.cpu().numpy()[:own], m
+
+
+def _run_batch_device(agent, num_steps_dev, num_steps, own):
+    """The same batch with `eval_metrics=device`: `HumanoidIm.post_physics_step` adds every step's error sums to per-env device totals
+    (phc_eval_accumulate) and the loop reads back two integers per step -- how many envs are alive and the longest clip among them -- from which
+    `curr_max` follows by the host loop's rules, so the batch runs exactly as many env steps.  One copy of the totals ends the batch."""
+    task, env = agent.task, agent.vec_env
+    lib, N = task._motion_lib, task.num_envs
+    U = lib._num_unique_motions
+    last = np.flatnonzero(lib._curr_motion_ids.cpu().numpy() == U - 1)   # (the clips of a batch are fixed: once, not per step)
+    task.begin_eval_accumulation(num_steps_dev, int(last[0]) + 1 if len(last) else N)
+    obs = env.reset()
+    curr = 0
+    while True:
+        res = agent.get_action_values(obs)
+        obs, r, done, info = env.step(agent.preprocess_actions(res["mus"]))
+        n_alive, curr_max = task.eval_status()
+        if n_alive:
+            if curr >= curr_max:   # (also "nobody below the bound is alive": status gives 0 there, the host loop curr - 1)
+                curr_max = curr + 1
+        else:
+            curr_max = num_steps.max()
+        curr += 1
+        if curr >= curr_max or not n_alive:
+            break
+    fail, sums, count = (t.cpu().numpy()[:own] for t in task.end_eval_accumulation())
+    return fail != 0, metrics_from_sums(sums, count, task.num_bodies)
+
+
 def evaluate(agent, output_dir=None, log=print):
     """Run the sweep with `agent`'s current policy.  Returns (eval_info dict, failed_keys).
 
     Several ranks: the batches of `num_envs` clips are dealt round-robin -- rank r evaluates batches r, r + world, ... of the
     length-sorted library --, every rank fills its clips' entries of dense per-clip arrays (failed flag, the five metrics), ONE all-reduce(sum)
     merges them, and every rank derives the same failed keys and re-weights its sampler identically.  (The reference evaluates on one process.)"""
-    task, env = agent.task, agent.vec_env
+    task = agent.task
+    # `+learning.params.config.eval_metrics=device`: the per-frame errors are summed on the device (phc_eval_accumulate) instead of copying every step's
+    # body positions to the host; same env steps, same results (DESIGN.md "Evaluation sweep: metrics on the device")
+    mode = str((getattr(agent, "config", None) or {}).get("eval_metrics", "host"))
+    if mode not in ("host", "device"):
+        raise ValueError(f"learning.params.config.eval_metrics must be host or device, not {mode!r}")
+    device_metrics = mode == "device"
     agent.set_eval()
     lib_train = task._motion_lib
     saved = dict(td=task._termination_distances.clone(), test=flags.test, im_eval=flags.im_eval, start_idx=task.start_idx)
@@ -85,42 +171,14 @@ def evaluate(agent, output_dir=None, log=print):
                 else:   # seek: forward_motion_samples() advances start_idx by num_envs and loads (humanoid_im.py:474-477)
                     task.start_idx = (bi - 1) * N
                     task.forward_motion_samples()
-                num_steps = lib.get_motion_num_steps().cpu().numpy()
-                terminate_state = torch.zeros(N, device=task.device, dtype=torch.bool)
-                preds, gts = [], []
-                obs = env.reset()
-                curr = 0
-                while True:
-                    res = agent.get_action_values(obs)
-                    obs, r, done, info = env.step(agent.preprocess_actions(res["mus"]))  # deterministic policy (is_determenistic=True)
-                    # a termination after the clip's last frame is not a failure (im_amp.py:248)
-                    term = torch.logical_and(torch.as_tensor(curr <= num_steps - 1, device=task.device), info["terminate"].bool())
-                    terminate_state |= term
-                    # how long this batch runs (im_amp.py:251-268): until the longest clip still alive has ended -- in the LAST batch, whose
-                    # envs past the library's final clip hold wrapped-around duplicates, only the envs up to that final clip count
-                    alive = (~terminate_state).cpu().numpy()
-                    if alive.any():
-                        last = np.flatnonzero(lib._curr_motion_ids.cpu().numpy() == U - 1)
-                        if len(last):
-                            bound = int(last[0]) + 1
-                            curr_max = num_steps[:bound][alive[:bound]].max() if alive[:bound].any() else curr - 1
-                        else:
-                            curr_max = num_steps[alive].max()
-                        if curr >= curr_max:
-                            curr_max = curr + 1
-                    else:
-                        curr_max = num_steps.max()
-                    preds.append(info["body_pos"])
-                    gts.append(info["body_pos_gt"])
-                    curr += 1
-                    if curr >= curr_max or not alive.any():
-                        break
-                P, G = np.stack(preds), np.stack(gts)
+                num_steps_dev = lib.get_motion_num_steps()
+                num_steps = num_steps_dev.cpu().numpy()
                 own = min(N, U - bi * N)                          # the envs past the library's end hold duplicates of its first clips
                 clips = slice(bi * N, bi * N + own)
-                failed[clips] = terminate_state.cpu().numpy()[:own]
-                frames = [max(min(int(num_steps[i]) - 1, P.shape[0]), 0) for i in range(own)]
-                m = compute_metrics_per_clip([P[:n, i] for i, n in enumerate(frames)], [G[:n, i] for i, n in enumerate(frames)])
+                if device_metrics:
+                    failed[clips], m = _run_batch_device(agent, num_steps_dev, num_steps, own)
+                else:
+                    failed[clips], m = _run_batch_host(agent, num_steps, own)
                 for k in METRICS:
                     per_clip[k][clips] = np.nan_to_num(m[k])
                     have[k][clips] = ~np.isnan(m[k])
@@ -143,6 +201,8 @@ def evaluate(agent, output_dir=None, log=print):
                      "eval/accel_dist": m_succ["accel_dist"], "eval/vel_dist": m_succ["vel_dist"], "eval/mpjpel_all": m_all["mpjpe_l"],
                      "eval/mpjpel_succ": m_succ["mpjpe_l"], "eval/mpjpe_pa": m_succ["mpjpe_pa"]}
     finally:
+        if device_metrics:
+            task.end_eval_accumulation()   # (an accumulation left open by an exception)
         task._termination_distances[:] = saved["td"]
         flags.test, flags.im_eval = saved["test"], saved["im_eval"]
         task._motion_lib = lib_train
