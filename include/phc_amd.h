@@ -313,6 +313,21 @@ int32_t phc_sim_step(const phc_model_t* model, const phc_sim_params_t* params, c
                      const float* actions /*[N,D]*/, const float* pd_action_offset /*[D]*/, const float* pd_action_scale /*[D]*/,
                      const int32_t* freeze_mask /*[D]*/, int32_t num_sim_calls, void* stream);
 
+/* phc_sim_step with an EXTERNAL WRENCH per rigid body (gym.apply_rigid_body_force_tensors in ENV_SPACE, phc/env/tasks/base_task.py:372-381; an addition to
+ * ABI 37).  ext_force [N,NB,3] in newtons acts at each body's CENTRE OF MASS, ext_torque [N,NB,3] in newton metres; both in env (= world) axes, each nullable.
+ * The wrench is constant over every sub-step of the first wrench_sim_calls simulate calls of the launch (clamped to 0..num_sim_calls; the gym clears applied
+ * forces after one simulate(), so a binding passes 1).  With both pointers NULL or wrench_sim_calls == 0 the call IS phc_sim_step: same checks, same launch,
+ * same bits.  The tensors are only read, and only at the [env, body] entries that exist.
+ * The wrench enters the bias force of the articulated-body recursion and nothing else: it depends on no state and adds no impedance, so the lagged sub-steps
+ * (inertia_lag) and every pass of the rigid contact model take it unchanged.  It is NOT part of contact_force (S4), force_sensor (S6) or dof_force (S5): those
+ * publish ground and body-body contact and the joint drives, as without a wrench.
+ * Both joint families, both group widths, both contact models, lag on and off.  PHC_EUNSUPPORTED (with a wrench): per-env body shapes
+ * (phc_model_t.num_shapes > 1) and lane_mapping 3. */
+int32_t phc_sim_step_wrench(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim,
+                            const float* actions /*[N,D]*/, const float* pd_action_offset /*[D]*/, const float* pd_action_scale /*[D]*/,
+                            const int32_t* freeze_mask /*[D]*/, int32_t num_sim_calls,
+                            const float* ext_force /*[N,NB,3]*/, const float* ext_torque /*[N,NB,3]*/, int32_t wrench_sim_calls, void* stream);
+
 /* S7 alone: forward kinematics from (root_states, dof_state) to rigid_body_state. */
 int32_t phc_refresh_body_state(const phc_model_t* model, const phc_sim_state_t* sim, void* stream);
 

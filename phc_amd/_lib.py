@@ -118,6 +118,7 @@ _SIGNATURES = {
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
     "phc_sample_time_interval": ([P(MotionLib), c_i32, c_p, c_p, c_p, c_p], c_i32),
     "phc_sim_step": ([P(Model), P(SimParams), P(SimState), c_p, c_p, c_p, c_p, c_i32, c_p], c_i32),
+    "phc_sim_step_wrench": ([P(Model), P(SimParams), P(SimState), c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p], c_i32),
     "phc_refresh_body_state": ([P(Model), P(SimState), c_p], c_i32),
     "phc_im_post_physics": ([P(Model), P(MotionLib), P(ImParams), P(SimState), P(ImBuffers), c_p], c_i32),
     "phc_amp_ref_table": ([P(Model), P(MotionLib), P(ImParams), c_i64, c_p, c_p, c_p], c_i32),

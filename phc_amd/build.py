@@ -11,14 +11,16 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #   task kernels: parity with the reference's torch ops is pinned at 1e-5 and torch does not fuse multiply-add, so
 #     -ffp-contract=off (e.g. sqrt(1 - w*w) in quat_to_angle_axis is cancellation-prone: a contracted fma moves exp-map
 #     outputs by 1e-3); -fno-slp-vectorize avoids v_pk_* register marshalling (reset 68 -> 49 us, post-physics 35 -> 27 us).
-#   stepper: see the header of phc_sim.hip (-ffast-math -fno-slp-vectorize: 158 -> 109 us).
+#   stepper: see the header of phc_sim.hip (-ffast-math -fno-slp-vectorize: 158 -> 109 us).  phc_sim_wrench.hip holds the external-wrench instantiations of the
+#     same kernel (phc_sim_kernel.h) and is compiled with the same flags.
 #   learner kernels: bandwidth-bound passes; IEEE division / no contraction so the normalised values equal torch's.
 #   matrix-core kernels (phc_gemm.hip): no contraction either (the fp32 slab and bias sums are plain adds in a fixed order).
 #   renderer (phc_render.hip, off the training path): IEEE fp32 (no fast-math): its error bound assumes correctly rounded sqrt / division.
 #   evaluation metrics (phc_eval.hip): no contraction -- its reference positions are bit-equal to phc_motion_state's.
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
+           "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", "phc_eval.h", "phc_group.h", os.path.join("..", "..", "include", "phc_amd.h")]
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", "phc_sim_kernel.h", "phc_eval.h", "phc_group.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

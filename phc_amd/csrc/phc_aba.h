@@ -214,7 +214,8 @@ PHC_HD void aba_load_model(AbaLane& L, const phc_model_t& m, int j, bool reroot 
 // revolute extras (template JT == PHC_JT_REVOLUTE paths only)
 // convenience overload: constants read from the model at every call
 template <int JT, bool RIGID = false>
-PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params_t& prm, float dt, int j, bool new_sim_call, bool reroot = true, int pass = 0, bool lag = false);
+PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params_t& prm, float dt, int j, bool new_sim_call, bool reroot = true, int pass = 0, bool lag = false,
+                          bool ext_on = false, V3 ext_f = V3(), V3 ext_t = V3());
 
 PHC_HD void aba_load_model_rev(AbaLane& L, const phc_model_t& m, int j) {
     const float* f = model_body(m, j);
@@ -485,6 +486,16 @@ PHC_HD CpMask cp_touching_batched(const M3& R, float pz, const float* cp, int n)
     return touching;
 }
 
+// ---- external wrench on a body (phc_sim_step_wrench, include/phc_amd.h): force F at the body's CENTRE OF MASS and torque T, world axes ----
+// It enters the bias force only, like the body-body contact wrench in aba_body_init: with so = R off the solver-reference offset and c = R com,
+//     p^A.f -= F,   p^A.n -= (T + c x F) - so x F = T + (c - so) x F = T + (mc x F) / mass,      mc = R m (com - off): aba_body_init's.
+// A given wrench depends on no state and adds no impedance: I^A, D^-1, the lagged sub-steps and the passes of the rigid contact model take it unchanged.  It is no
+// part of fcontact (S4), of the force sensors (S6) or of tau_local (S5).
+PHC_HD void aba_add_wrench(AbaLane& L, V3 mc, float mass, V3 F, V3 T) {
+    L.pA.f -= F;
+    L.pA.n -= T + cross(mc, F) * (1.0f / mass);
+}
+
 // ---- per-body initialisation of I^A, p^A and of the joint drive (no communication) ----
 // `new_sim_call`: first sub-step of a gym.simulate call -- the explicit `pd` torque is recomputed there (humanoid.py:1608-1616).
 // `f`: the body's PHC_BODY_FLOATS constants -- straight from the model (L2) or a register copy the caller made once per launch;
@@ -496,9 +507,12 @@ PHC_HD CpMask cp_touching_batched(const M3& R, float pz, const float* cp, int n)
 // `lag` (phc_sim_params_t.inertia_lag, penalty contact only): a sub-step that keeps the articulated inertias I^A and the joint-space inverses D^-1 of the
 // previous sub-step (aba_backward_level's bias-only form).  Only p^A and the joint drive are formed here then: bias force and gravity at the current
 // state, the explicit part F0 of the contact law for the points whose impedance the kept I^A holds (L.c_touch), body-body forces, drive torque.
+// `ext_on`, `ext_f`, `ext_t`: the body's external wrench of this sub-step (aba_add_wrench; phc_sim_step_wrench only).  Applied with the bias force, in every pass and
+// every lagged sub-step (p^A starts afresh there): R m (com - off) is at hand at that point, and behind the contact points it would have to be kept or formed again.
 template <int JT, bool RIGID>
 PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params_t& prm, float dt, int j, bool new_sim_call,
-                          const float* f, int cp_start, int cp_total, bool reroot, int pass, bool lag = false) {
+                          const float* f, int cp_start, int cp_total, bool reroot, int pass, bool lag = false,
+                          bool ext_on = false, V3 ext_f = V3(), V3 ext_t = V3()) {
     constexpr bool BATCH = aba_batched_constants<JT, RIGID>();
     const float mass = BATCH ? L.mass : f[3];
     // every spatial quantity of the body is taken about its solver reference point o = p + R off (the origin unless the body is reversed)
@@ -533,6 +547,7 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
     V3 g = v3(0.f, 0.f, prm.gravity_z);
     L.pA.n = cross(L.w, sym_mul(Io, L.w)) - cross(mc, g);
     L.pA.f = cross(L.w, cross(L.w, mc)) - g * mass;
+    if (ext_on) aba_add_wrench(L, mc, mass, ext_f, ext_t);
     // ground contact: plane z = 0, normal +z
     L.fcontact = v3(0.f, 0.f, 0.f);
     if (RIGID) {
@@ -668,8 +683,9 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
 }
 
 template <int JT, bool RIGID>
-PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params_t& prm, float dt, int j, bool new_sim_call, bool reroot, int pass, bool lag) {
-    aba_body_init<JT, RIGID>(L, m, prm, dt, j, new_sim_call, model_body(m, j), model_tab(m, 8, j), model_tab(m, 9, j), reroot, pass, lag);
+PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params_t& prm, float dt, int j, bool new_sim_call, bool reroot, int pass, bool lag,
+                          bool ext_on, V3 ext_f, V3 ext_t) {
+    aba_body_init<JT, RIGID>(L, m, prm, dt, j, new_sim_call, model_body(m, j), model_tab(m, 8, j), model_tab(m, 9, j), reroot, pass, lag, ext_on, ext_f, ext_t);
 }
 // rigid contact model: S4 net ground force of the body from the final solve of the sub-step (+ the body-body forces, as the penalty model
 // publishes), and S6: the force sensors read the same wrench (about the body origin, in the body frame)

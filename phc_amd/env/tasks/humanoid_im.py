@@ -444,6 +444,16 @@ class HumanoidIm:
             # (the rigid model's per-point active / released sets are 32-bit masks: a point beyond bit 31 could never be released)
             raise ValueError("solver.contact=tgs supports at most 32 ground-contact points per body; this model has more (use the penalty model)")
 
+        # ---- external wrenches (gym.apply_rigid_body_force_tensors; phc_sim_step_wrench) and the push schedule `+perturb.*` (phc_amd/perturb.py) ----
+        self._ext_force = self._ext_torque = None   # [N, NB, 3] buffers of the one-shot API, made at its first call
+        self._ext_pending = None                    # (force given, torque given, sim_calls) for the next step() only
+        self._push = None
+        pcfg = cfg.get("perturb", None)
+        if pcfg:
+            self._check_wrench_supported("perturb")
+            from ...perturb import PushSchedule
+            self._push = PushSchedule(pcfg, N, list(self._body_names), self.dt, dev, default_seed=int(cfg.get("seed", 0)))
+
         # ---- action scaling (A1) + freeze masks (humanoid.py:1331-1409,1549-1554) ----
         self.dof_limits_lower, self.dof_limits_upper = (torch.from_numpy(x).to(dev) for x in self.model.dof_limits())
         self.dof_limits = torch.stack([self.dof_limits_lower, self.dof_limits_upper], dim=-1)
@@ -815,6 +825,8 @@ class HumanoidIm:
             self.actions = torch.clip(self.actions, -10, 10)   # humanoid.py:1568-1570
         if self._occl_training:   # humanoid_im.py:1112-1113
             self._update_occl_training()
+        if self._push is not None:   # (an env reset since the last step has progress 0: its push ends, a new pause is drawn)
+            self._push.advance(self.progress_buf == 0)
 
     def _update_occl_training(self):
         """humanoid_im.py:1081-1092: occlusion spans of 30-59 steps start with probability occl_training_prob per tracked body and step (never the
@@ -834,8 +846,47 @@ class HumanoidIm:
             off, scale = self._torque_target_offset, self._torque_target_scale
         else:
             off, scale = self._pd_action_offset, self._pd_action_scale
-        L.check(self._lib.phc_sim_step(self._model_struct, self._sim_params, self._sim_struct, a.data_ptr(), off.data_ptr(), scale.data_ptr(),
-                                       self._freeze_mask.data_ptr(), self.control_freq_inv, _stream()), "phc_sim_step")
+        if self._push is not None:      # a schedule: the same launch in every step, its force buffer zero between pushes
+            wrench = (self._push.force.data_ptr(), None, self.control_freq_inv)
+        elif self._ext_pending is not None:   # one-shot wrench: this step only
+            has_f, has_t, calls = self._ext_pending
+            wrench = (self._ext_force.data_ptr() if has_f else None, self._ext_torque.data_ptr() if has_t else None, calls)
+            self._ext_pending = None
+        else:
+            L.check(self._lib.phc_sim_step(self._model_struct, self._sim_params, self._sim_struct, a.data_ptr(), off.data_ptr(), scale.data_ptr(),
+                                           self._freeze_mask.data_ptr(), self.control_freq_inv, _stream()), "phc_sim_step")
+            return
+        L.check(self._lib.phc_sim_step_wrench(self._model_struct, self._sim_params, self._sim_struct, a.data_ptr(), off.data_ptr(), scale.data_ptr(),
+                                              self._freeze_mask.data_ptr(), self.control_freq_inv, *wrench, _stream()), "phc_sim_step_wrench")
+
+    def _check_wrench_supported(self, what):
+        """phc_sim_step_wrench has no instantiation for per-env body shapes or for the three-wavefront experiment build (include/phc_amd.h)."""
+        if self._env_shape is not None:
+            raise NotImplementedError(f"{what}: external wrenches are not built for per-env body shapes (robot.has_shape_variation)")
+        if int(self._sim_params.lane_mapping) == 3:
+            raise NotImplementedError(f"{what}: external wrenches are not built for solver.lane_mapping=3")
+
+    def apply_rigid_body_force_tensors(self, forces=None, torques=None, sim_calls=1):
+        """gym.apply_rigid_body_force_tensors(sim, forces, torques, ENV_SPACE) (base_task.py:372-381): `forces` [N, NB, 3] in newtons acting at the bodies' centres
+        of mass, `torques` [N, NB, 3] in newton metres, env axes; either may be None.  They are copied into buffers of the task, act in the NEXT step() only -- over
+        its first `sim_calls` simulate calls (the gym clears applied forces after one simulate()) -- and are then cleared.  They are no part of the published contact
+        forces, force sensors or dof forces."""
+        if self._push is not None:
+            raise ValueError("apply_rigid_body_force_tensors on a task with a push schedule (+perturb.*): the two durations do not mix in one launch")
+        self._check_wrench_supported("apply_rigid_body_force_tensors")
+        if forces is None and torques is None:
+            self._ext_pending = None
+            return
+        shape = (self.num_envs, self.num_bodies, 3)
+        for name, src in (("_ext_force", forces), ("_ext_torque", torques)):
+            if src is None:
+                continue
+            if tuple(src.shape) != shape:
+                raise ValueError(f"apply_rigid_body_force_tensors: expected tensors of shape {shape}, got {tuple(src.shape)}")
+            if getattr(self, name) is None:
+                setattr(self, name, torch.zeros(shape, dtype=torch.float32, device=self.device))
+            getattr(self, name).copy_(src)
+        self._ext_pending = (forces is not None, torques is not None, int(sim_calls))
 
     def post_physics_step(self):
         if (flags.im_eval, flags.no_collision_check) != self._flag_state:

@@ -1158,6 +1158,9 @@ class IMAmpAgent:
         `Humanoid.pth` every min(50, save_best_after) epochs; every `save_frequency` epochs (save_intermediate) also
         `Humanoid_{epoch:08d}.pth` and the evaluation sweep `eval()`, which re-weights the clip sampling (auto-PMCP, im_amp.py:126-132)
         and writes `failed_{epoch:010d}.pkl`."""
+        if getattr(self.task, "_push", None) is not None:
+            # the captured rollout graph freezes the launch sequence and the state of the schedule's generator
+            raise NotImplementedError("training under a push schedule (+perturb.*) is not built: pushes act in play (test=True) and in the evaluation sweep")
         self.init_train()
         c = self.config
         save_freq, save_best_after = int(c.get("save_frequency", 0)), int(c.get("save_best_after", 100))

@@ -160,6 +160,8 @@ def evaluate(agent, output_dir=None, log=print):
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     num_batches = (U + N - 1) // N
+    push = getattr(task, "_push", None)                         # `+perturb.*` (phc_amd/perturb.py): the sweep then runs under scheduled pushes
+    pushes0 = int(push.pushes) if push is not None else 0
     failed = np.zeros(U, dtype=np.float64)                      # 1 where the clip terminated before its last frame
     per_clip = {k: np.zeros(U) for k in METRICS}                # metric value of every clip this rank evaluated ...
     have = {k: np.zeros(U) for k in METRICS}                    # ... and whether the clip has that metric
@@ -200,6 +202,8 @@ def evaluate(agent, output_dir=None, log=print):
         eval_info = {"eval/success_rate": float(1 - term.mean()), "eval/mpjpe_all": m_all["mpjpe_g"], "eval/mpjpe_succ": m_succ["mpjpe_g"],
                      "eval/accel_dist": m_succ["accel_dist"], "eval/vel_dist": m_succ["vel_dist"], "eval/mpjpel_all": m_all["mpjpe_l"],
                      "eval/mpjpel_succ": m_succ["mpjpe_l"], "eval/mpjpe_pa": m_succ["mpjpe_pa"]}
+        if push is not None:
+            eval_info["perturb_pushes"] = int(push.pushes) - pushes0   # pushes started during this rank's batches, all envs
     finally:
         if device_metrics:
             task.end_eval_accumulation()   # (an accumulation left open by an exception)

@@ -75,6 +75,7 @@ def main(argv=None):
 def play(agent, task, env, steps=300):
     """Deterministic-policy rollout (players.PpoPlayerContinuous with is_determenistic=True): mean reward and episode length."""
     agent.set_eval()
+    pushes0 = int(task._push.pushes) if getattr(task, "_push", None) is not None else 0
     obs = env.reset()
     rew_sum = torch.zeros(task.num_envs, device=task.device)
     ep_len = torch.zeros(task.num_envs, device=task.device)
@@ -94,7 +95,10 @@ def play(agent, task, env, steps=300):
                 obs = env.reset(ids)
     lens = torch.cat(lens) if lens else ep_len
     rews = torch.cat(rews) if rews else rew_sum
-    return {"episodes": int(lens.numel()), "mean_episode_length": float(lens.mean()), "mean_episode_reward": float(rews.mean()), "steps": steps}
+    out = {"episodes": int(lens.numel()), "mean_episode_length": float(lens.mean()), "mean_episode_reward": float(rews.mean()), "steps": steps}
+    if getattr(task, "_push", None) is not None:   # `+perturb.*` (phc_amd/perturb.py): pushes started during the rollout, all envs
+        out["perturb_pushes"] = int(task._push.pushes) - pushes0
+    return out
 
 
 if __name__ == "__main__":
