@@ -8,13 +8,16 @@
 #include <omp.h>
 #include "../../phc_amd/csrc/phc_aba.h"
 #include "../../phc_amd/csrc/phc_im.h"
+#include "../../phc_amd/csrc/phc_sim_check.h"
 
 using namespace phc;
 
-// Stepper: same phase sequence as k_sim_step, lanes looped inside each phase.
+// Stepper: same phase sequence as k_sim_step, lanes looped inside each phase.  `ext_force` / `ext_torque` ([N, NB, 3], nullable) act in the first `wrench_nsub`
+// sub-steps, handed to aba_body_init the way the kernel's WRENCH instantiations hand them over.
 template <int JT>
 static int emu_sim_step_t(const phc_model_t* model_all, const phc_sim_params_t* prm, const phc_sim_state_t* sim, const float* actions,
-                          const float* pd_off, const float* pd_scale, const int32_t* freeze, int num_sim_calls, int do_step) {
+                          const float* pd_off, const float* pd_scale, const int32_t* freeze, int num_sim_calls, int do_step,
+                          const float* ext_force = nullptr, const float* ext_torque = nullptr, int wrench_nsub = 0) {
     const int nb = model_all->num_bodies, nd = model_all->num_dof;
     const int ndj = JT == PHC_JT_REVOLUTE ? 1 : 3;
 #pragma omp parallel for schedule(static)
@@ -68,10 +71,14 @@ static int emu_sim_step_t(const phc_model_t* model_all, const phc_sim_params_t* 
                 const bool rigid = prm->contact_model == 1;
                 const int passes = rigid ? (prm->contact_iterations < 1 ? 1 : prm->contact_iterations) : 1;
                 const bool lag = !rigid && prm->inertia_lag != 0 && (s % prm->substeps) != 0;
+                const bool ext_on = s < wrench_nsub;   // the wrench of this sub-step, as the kernel reads it: the body's own entry of each tensor
                 for (int pass = 0; pass < passes; ++pass) {
                     for (int j = 0; j < nb; ++j) {
-                        if (rigid) aba_body_init<JT, true>(L[j], *model, *prm, dt, j, s % prm->substeps == 0, true, pass);
-                        else aba_body_init<JT, false>(L[j], *model, *prm, dt, j, s % prm->substeps == 0, true, 0, lag);
+                        V3 F = v3(0.f, 0.f, 0.f), T = v3(0.f, 0.f, 0.f);
+                        if (ext_on && ext_force) { const float* p = ext_force + (env * nb + j) * 3; F = v3(p[0], p[1], p[2]); }
+                        if (ext_on && ext_torque) { const float* p = ext_torque + (env * nb + j) * 3; T = v3(p[0], p[1], p[2]); }
+                        if (rigid) aba_body_init<JT, true>(L[j], *model, *prm, dt, j, s % prm->substeps == 0, true, pass, false, ext_on, F, T);
+                        else aba_body_init<JT, false>(L[j], *model, *prm, dt, j, s % prm->substeps == 0, true, 0, lag, ext_on, F, T);
                     }
                     if (JT == PHC_JT_SPHERICAL && rerooted && pass == 0) {
                         for (int j = 0; j < nb; ++j) aba_publish_drive(L[j], j, x);
@@ -223,17 +230,33 @@ int emu_amp_ref_table(const phc_model_t* model, const phc_motion_lib_t* lib, con
     return 0;
 }
 
+static int emu_sim_step_jt(const phc_model_t* model, const phc_sim_params_t* prm, const phc_sim_state_t* sim, const float* actions, const float* pd_off,
+                           const float* pd_scale, const int32_t* freeze, int num_sim_calls, int do_step, const float* ext_force, const float* ext_torque,
+                           int wrench_nsub) {
+    if (model->num_dof == model->num_bodies - 1 && model->num_bodies > 2)
+        return emu_sim_step_t<PHC_JT_REVOLUTE>(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, do_step, ext_force, ext_torque, wrench_nsub);
+    return emu_sim_step_t<PHC_JT_SPHERICAL>(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, do_step, ext_force, ext_torque, wrench_nsub);
+}
+
+// do_step = 1: phc_sim_step, with its refusals (phc_sim_check.h); do_step = 0: phc_refresh_body_state
 int emu_sim_step(const phc_model_t* model, const phc_sim_params_t* prm, const phc_sim_state_t* sim, const float* actions,
                  const float* pd_off, const float* pd_scale, const int32_t* freeze, int num_sim_calls, int do_step) {
-    if (do_step) {   // the option checks of phc_sim_step (phc_sim.hip), mirrored: same refusals on both backends
-        if (prm->contact_model == 1 && prm->inertia_lag) return PHC_EUNSUPPORTED;
-        if (prm->inertia_lag && prm->lane_mapping == 3) return PHC_EUNSUPPORTED;
-        if (prm->contact_model == 1 && model->max_body_contact_pts > 32) return PHC_EUNSUPPORTED;
-        if (prm->inertia_lag && model->max_body_contact_pts > PHC_CP_BITS) return PHC_EUNSUPPORTED;
+    if (do_step) {
+        const int rc = check_sim_step(model, prm, sim, actions, pd_off, pd_scale, num_sim_calls);
+        if (rc) return rc;
     }
-    if (model->num_dof == model->num_bodies - 1 && model->num_bodies > 2)
-        return emu_sim_step_t<PHC_JT_REVOLUTE>(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, do_step);
-    return emu_sim_step_t<PHC_JT_SPHERICAL>(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, do_step);
+    return emu_sim_step_jt(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, do_step, nullptr, nullptr, 0);
+}
+
+// phc_sim_step_wrench: no wrench is exactly emu_sim_step
+int emu_sim_step_wrench(const phc_model_t* model, const phc_sim_params_t* prm, const phc_sim_state_t* sim, const float* actions, const float* pd_off,
+                        const float* pd_scale, const int32_t* freeze, int num_sim_calls, const float* ext_force, const float* ext_torque,
+                        int wrench_sim_calls) {
+    const int calls = wrench_sim_calls < 0 ? 0 : (wrench_sim_calls > num_sim_calls ? num_sim_calls : wrench_sim_calls);
+    if ((!ext_force && !ext_torque) || calls == 0) return emu_sim_step(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, 1);
+    const int rc = check_sim_step_wrench(model, prm, sim, actions, pd_off, pd_scale, num_sim_calls);
+    if (rc) return rc;
+    return emu_sim_step_jt(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, 1, ext_force, ext_torque, calls * prm->substeps);
 }
 
 }  // extern "C"

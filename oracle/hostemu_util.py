@@ -52,6 +52,7 @@ def emu():
         lib.emu_amp_obs_demo.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), i32, vp, vp, vp]
         lib.emu_amp_ref_table.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), C.c_int64, vp, vp]
         lib.emu_sim_step.argtypes = [PS(L.Model), PS(L.SimParams), PS(L.SimState), vp, vp, vp, vp, i32, i32]
+        lib.emu_sim_step_wrench.argtypes = [PS(L.Model), PS(L.SimParams), PS(L.SimState), vp, vp, vp, vp, i32, vp, vp, i32]
         _emu = lib
     return _emu
 
@@ -107,7 +108,9 @@ def emu64():
     global _emu64
     if _emu64 is None:
         lib = C.CDLL(build64())
-        lib.emu_sim_step.argtypes = [C.POINTER(Model64), C.POINTER(SimParams64), C.POINTER(SimState64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+        structs, vp = [C.POINTER(Model64), C.POINTER(SimParams64), C.POINTER(SimState64)], C.c_void_p
+        lib.emu_sim_step.argtypes = structs + [vp, vp, vp, vp, C.c_int32, C.c_int32]
+        lib.emu_sim_step_wrench.argtypes = structs + [vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int32]
         _emu64 = lib
     return _emu64
 
@@ -119,15 +122,39 @@ def _to64(s, cls64):
     return d
 
 
-def sim_step_f64(model, params, root_states, dof_state, pd_target, num_sim_calls=2, kp_scale=1.0, kd_scale=1.0):
-    """`phc_sim_step` for n envs through the double-precision build: `model` an ArticulationModel, `params` the fp32 `phc_sim_params_t` (abi.sim_params_struct),
-    states as float arrays [n, 13] / [n, D, 2] / [n, D].  -> dict(root, dof, rbs, cf, df) of float64 arrays."""
-    ints, floats = model.pack(kp_scale, kd_scale, float_dtype=np.float64)
-    ms = _to64(abi.model_struct(ints, floats, model.num_bodies, model.num_dof, model.max_level, len(model.contact_body)), Model64)
+def host_sim_step(model, params, root_states, dof_state, pd_target, num_sim_calls=2, kp_scale=1.0, kd_scale=1.0, f64=True, force=None, torque=None,
+                  wrench_sim_calls=None, gravity_z=None):
+    """`phc_sim_step` for n envs on the host, through the double-precision build or (`f64=False`) the single-precision one: `model` an ArticulationModel, `params`
+    the fp32 `phc_sim_params_t` (abi.sim_params_struct), states as float arrays [n, 13] / [n, D, 2] / [n, D].  `wrench_sim_calls` not None: `phc_sim_step_wrench`
+    with `force` / `torque` ([n, NB, 3] or None).  `gravity_z` (fp64 only): overrides the parameter struct's value at full double precision.
+    -> dict(root, dof, rbs, cf, df, pd, floats) of arrays of the build's precision."""
+    T = np.float64 if f64 else np.float32
+    ints, floats = model.pack(kp_scale, kd_scale, float_dtype=T)
+    ms = abi.model_struct(ints, floats, model.num_bodies, model.num_dof, model.max_level, len(model.contact_body))
     n, nb, nd = np.asarray(root_states).shape[0], model.num_bodies, model.num_dof
-    a = dict(root=np.array(root_states, dtype=np.float64, order="C"), dof=np.array(dof_state, dtype=np.float64, order="C"), rbs=np.zeros((n, nb, 13)),
-             cf=np.zeros((n, nb, 3)), df=np.zeros((n, nd)), pd=np.array(pd_target, dtype=np.float64, order="C"))
-    sim = _to64(abi.sim_state_struct(n, a["root"], a["dof"], a["rbs"], a["cf"], a["df"], a["pd"]), SimState64)
-    rc = emu64().emu_sim_step(C.byref(ms), C.byref(_to64(params, SimParams64)), C.byref(sim), None, None, None, None, int(num_sim_calls), 1)
+    a = dict(root=np.array(root_states, dtype=T, order="C"), dof=np.array(dof_state, dtype=T, order="C"), rbs=np.zeros((n, nb, 13), T),
+             cf=np.zeros((n, nb, 3), T), df=np.zeros((n, nd), T), pd=np.array(pd_target, dtype=T, order="C"), floats=floats)
+    sim = abi.sim_state_struct(n, a["root"], a["dof"], a["rbs"], a["cf"], a["df"], a["pd"])
+    prm = params
+    if f64:
+        ms, sim, prm = _to64(ms, Model64), _to64(sim, SimState64), _to64(params, SimParams64)
+        if gravity_z is not None:
+            prm.gravity_z = float(gravity_z)
+    else:
+        assert gravity_z is None
+    lib = emu64() if f64 else emu()
+    if wrench_sim_calls is None:
+        assert force is None and torque is None
+        rc = lib.emu_sim_step(C.byref(ms), C.byref(prm), C.byref(sim), None, None, None, None, int(num_sim_calls), 1)
+    else:
+        fo = None if force is None else np.array(force, dtype=T, order="C")
+        to = None if torque is None else np.array(torque, dtype=T, order="C")
+        rc = lib.emu_sim_step_wrench(C.byref(ms), C.byref(prm), C.byref(sim), None, None, None, None, int(num_sim_calls), abi.ptr(fo), abi.ptr(to),
+                                     int(wrench_sim_calls))
     assert rc == 0, rc
     return a
+
+
+def sim_step_f64(model, params, root_states, dof_state, pd_target, num_sim_calls=2, kp_scale=1.0, kd_scale=1.0):
+    """`host_sim_step` through the double-precision build, no wrench.  -> dict(root, dof, rbs, cf, df) of float64 arrays."""
+    return host_sim_step(model, params, root_states, dof_state, pd_target, num_sim_calls, kp_scale, kd_scale)

@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", "phc_sim_kernel.h", "phc_eval.h", "phc_group.h", os.path.join("..", "..", "include", "phc_amd.h")]
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_eval.h", "phc_group.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

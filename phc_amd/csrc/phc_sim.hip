@@ -54,95 +54,16 @@ extern "C" int32_t phc_debug_timeline(unsigned long long* out512, int32_t block)
 
 // the kernel; with PHC_SIM_PROFILE the hooks above are compiled into it
 #include "phc_sim_kernel.h"
-
-template <bool STEP, int JT, bool SHAPES, bool RIGID>
-static void sim_launch_cm(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions,
-                          const float* off, const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream,
-                          const int64_t* env_ids, int num_listed) {
-    const int64_t groups = env_ids ? num_listed : sim->num_envs;
-    const bool wide = model->num_bodies > 32;   // more bodies than a 32-lane group holds: one env per wavefront
-    const bool occ3 = STEP && !RIGID && !SHAPES && JT == PHC_JT_SPHERICAL && !wide && prm.lane_mapping == 3;   // (experiment knob, see k_sim_step)
-    const bool lag = STEP && !RIGID && prm.inertia_lag != 0;
-    if (occ3)
-        hipLaunchKernelGGL((k_sim_step<STEP, JT, 32, SHAPES, RIGID, (STEP && !RIGID && !SHAPES && JT == PHC_JT_SPHERICAL) ? 3 : 2>), dim3((groups + 1) / 2), dim3(64), 0, stream,
-                           *model, prm, *sim, actions, off, scale, freeze, num_sim_calls, env_ids, num_listed, WrenchArgs<false>());
-    else if (lag && wide)
-        hipLaunchKernelGGL((k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, STEP && !RIGID>), dim3(groups), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze,
-                           num_sim_calls, env_ids, num_listed, WrenchArgs<false>());
-    else if (lag)
-        hipLaunchKernelGGL((k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, STEP && !RIGID>), dim3((groups + 1) / 2), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze,
-                           num_sim_calls, env_ids, num_listed, WrenchArgs<false>());
-    else if (wide)
-        hipLaunchKernelGGL((k_sim_step<STEP, JT, 64, SHAPES, RIGID>), dim3(groups), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze,
-                           num_sim_calls, env_ids, num_listed, WrenchArgs<false>());
-    else
-        hipLaunchKernelGGL((k_sim_step<STEP, JT, 32, SHAPES, RIGID>), dim3((groups + 1) / 2), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze,
-                           num_sim_calls, env_ids, num_listed, WrenchArgs<false>());
-}
-template <bool STEP, int JT, bool SHAPES>
-static void sim_launch_jt(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions,
-                          const float* off, const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream,
-                          const int64_t* env_ids, int num_listed) {
-    if (STEP && prm.contact_model == 1)   // rigid ground contact: its own instantiation, the penalty kernel is untouched by it
-        sim_launch_cm<STEP, JT, SHAPES, STEP>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed);
-    else
-        sim_launch_cm<STEP, JT, SHAPES, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed);
-}
-
-template <bool STEP>
-static void sim_launch(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions,
-                       const float* off, const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream,
-                       const int64_t* env_ids = nullptr, int num_listed = 0) {
-    if (model->num_dof == model->num_bodies - 1 && model->num_bodies > 2)  // one revolute joint per body (robots; one shape)
-        sim_launch_jt<STEP, PHC_JT_REVOLUTE, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed);
-    else if (model->num_shapes > 1 && sim->env_shape != nullptr)   // per-env body shapes (SMPL family)
-        sim_launch_jt<STEP, PHC_JT_SPHERICAL, true>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed);
-    else
-        sim_launch_jt<STEP, PHC_JT_SPHERICAL, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed);
-}
-
-static inline int32_t launch_status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int32_t)e;
-}
+#include "phc_sim_check.h"
 
 extern "C" {
-
-static int32_t check_model(const phc_model_t* m) {
-    if (!m || m->num_bodies < 1 || m->num_bodies > PHC_MAX_BODIES || !m->ints || !m->floats) return PHC_EINVAL;
-    // all-spherical (SMPL family) or all-revolute (H1 / G1) articulations
-    if (m->num_dof != 3 * (m->num_bodies - 1) && m->num_dof != m->num_bodies - 1) return PHC_EUNSUPPORTED;
-    if (m->num_shapes > 1 && m->num_dof != 3 * (m->num_bodies - 1)) return PHC_EUNSUPPORTED;   // per-env shapes: SMPL family only
-    if (m->num_shapes > 1 && (m->int_stride <= 0 || m->float_stride <= 0)) return PHC_EINVAL;
-    return 0;
-}
-
-// the argument and option checks of a stepping launch: phc_sim_step and, from its own translation unit, phc_sim_step_wrench (not part of the public header)
-int32_t phc_sim_step_check(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim, const float* actions,
-                              const float* pd_action_offset, const float* pd_action_scale, int32_t num_sim_calls) {
-    int32_t rc = check_model(model);
-    if (rc) return rc;
-    if (!params || !sim || sim->num_envs < 0 || params->substeps < 1 || num_sim_calls < 0) return PHC_EINVAL;
-    if (actions && (!pd_action_offset || !pd_action_scale)) return PHC_EINVAL;
-    if (sim->num_envs == 0) return 0;
-    // pairs are dealt round-robin to the lanes of an env's group: PHC_SC_MAX_PER_LANE each
-    if (params->self_collision && model->num_collision_pairs > PHC_SC_MAX_PER_LANE * (model->num_bodies > 32 ? 64 : 32)) return PHC_EUNSUPPORTED;
-    if (params->lane_mapping != 0 && params->lane_mapping != 1 && params->lane_mapping != 3) return PHC_EUNSUPPORTED;   // (2 was the two-bodies-per-lane kernel of rounds 1-2: removed)
-    if (params->contact_model != 0 && params->contact_model != 1) return PHC_EUNSUPPORTED;
-    if (params->contact_model == 1 && (params->contact_iterations < 2 || !(params->contact_impedance > 0.f))) return PHC_EINVAL;
-    if (params->contact_model == 1 && params->inertia_lag) return PHC_EUNSUPPORTED;   // (the rigid model re-solves every sub-step contact_iterations times with fresh impedances)
-    if (params->inertia_lag && params->lane_mapping == 3) return PHC_EUNSUPPORTED;   // (the three-wavefront experiment build has no lagged instantiation: it would silently run fresh)
-    if (params->contact_model == 1 && model->max_body_contact_pts > 32) return PHC_EUNSUPPORTED;   // c_active / c_removed are 32-bit masks: a point beyond them could never be released
-    if (params->inertia_lag && model->max_body_contact_pts > PHC_CP_BITS) return PHC_EUNSUPPORTED;  // c_touch: tail points would alternate between full and no force
-    return 0;
-}
 
 int32_t phc_sim_step(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim, const float* actions,
                      const float* pd_action_offset, const float* pd_action_scale, const int32_t* freeze_mask,
                      int32_t num_sim_calls, void* stream) {
-    int32_t rc = phc_sim_step_check(model, params, sim, actions, pd_action_offset, pd_action_scale, num_sim_calls);
+    int32_t rc = check_sim_step(model, params, sim, actions, pd_action_offset, pd_action_scale, num_sim_calls);
     if (rc || sim->num_envs == 0) return rc;
-    sim_launch<true>(model, *params, sim, actions, pd_action_offset, pd_action_scale, freeze_mask, num_sim_calls, (hipStream_t)stream);
+    sim_launch<true, false>(model, *params, sim, actions, pd_action_offset, pd_action_scale, freeze_mask, num_sim_calls, (hipStream_t)stream, nullptr, 0, WrenchArgs<false>());
     return launch_status();
 }
 
@@ -153,7 +74,7 @@ int32_t phc_refresh_body_state(const phc_model_t* model, const phc_sim_state_t* 
     if (sim->num_envs == 0) return 0;
     phc_sim_params_t prm = {};
     prm.substeps = 1;
-    sim_launch<false>(model, prm, sim, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+    sim_launch<false, false>(model, prm, sim, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, nullptr, 0, WrenchArgs<false>());
     return launch_status();
 }
 
@@ -165,7 +86,7 @@ int32_t phc_refresh_body_state_indexed(const phc_model_t* model, const phc_sim_s
     if (num == 0) return 0;
     phc_sim_params_t prm = {};
     prm.substeps = 1;
-    sim_launch<false>(model, prm, sim, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, env_ids, num);
+    sim_launch<false, false>(model, prm, sim, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, env_ids, num, WrenchArgs<false>());
     return launch_status();
 }
 

@@ -1,5 +1,5 @@
 // phc_sim_kernel.h -- k_sim_step, the articulated-body stepper kernel (S10), and what it is made of outside phc_aba.h: the action -> PD-target map and the staged
-// epilogue.  A header because the kernel is instantiated in two translation units that are compiled with the same flags (phc_amd/build.py): phc_sim.hip holds every
+// epilogue; behind the kernel, the chooser of the instantiation to launch.  A header because the kernel is instantiated in two translation units that are compiled with the same flags (phc_amd/build.py): phc_sim.hip holds every
 // instantiation phc_sim_step and the refresh entry points launch, phc_sim_wrench.hip the WRENCH twins of phc_sim_step_wrench.  Two units, so that adding the twins
 // leaves the instruction streams of the plain instantiations exactly what they were (the compiler's output for one kernel depends on what else its module holds;
 // profiles/ext_wrench/README.md).
@@ -326,4 +326,53 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     if (STEP && !RIGID && active && sim.force_sensor != nullptr) aba_publish_sensors(L, model, prm, sim, prm.sim_dt / (float)prm.substeps, env, body);   // S6
     PHC_PROF(8)
     if (STEP) { PHC_PROF_FLUSH }
+}
+
+// ------------------------------------------------------------------------------------------
+// The launch chooser: which instantiation a model and its options run.  One chooser for both translation units; WRENCH = true names only the instantiations
+// phc_sim_step_wrench launches (one env-shape block, two wavefronts per SIMD: it refuses the rest), so each unit holds exactly its own kernels.
+// ------------------------------------------------------------------------------------------
+template <bool STEP, int JT, bool SHAPES, bool RIGID, bool WRENCH>
+static void sim_launch_cm(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions, const float* off,
+                          const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream, const int64_t* env_ids, int num_listed,
+                          const WrenchArgs<WRENCH>& wr) {
+    const int64_t groups = env_ids ? num_listed : sim->num_envs;
+    const bool wide = model->num_bodies > 32;   // more bodies than a 32-lane group holds: one env per wavefront
+    constexpr bool LAG = STEP && !RIGID;
+    const bool lag = LAG && prm.inertia_lag != 0;
+    auto launch = [&](auto kernel, int64_t blocks) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze, num_sim_calls, env_ids, num_listed, wr);
+    };
+    if constexpr (!WRENCH && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // (experiment knob, see OCC above)
+        if (!wide && prm.lane_mapping == 3) return launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 3>, (groups + 1) / 2);
+    if (lag && wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, LAG, WRENCH>, groups);
+    else if (lag) launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, LAG, WRENCH>, (groups + 1) / 2);
+    else if (wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, false, WRENCH>, groups);
+    else launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, false, WRENCH>, (groups + 1) / 2);
+}
+
+template <bool STEP, int JT, bool SHAPES, bool WRENCH>
+static void sim_launch_jt(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions, const float* off,
+                          const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream, const int64_t* env_ids, int num_listed,
+                          const WrenchArgs<WRENCH>& wr) {
+    if (STEP && prm.contact_model == 1)   // rigid ground contact: its own instantiation, the penalty kernel is untouched by it
+        sim_launch_cm<STEP, JT, SHAPES, STEP, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+    else
+        sim_launch_cm<STEP, JT, SHAPES, false, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+}
+template <bool STEP, bool WRENCH>
+static void sim_launch(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions, const float* off,
+                       const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream, const int64_t* env_ids, int num_listed,
+                       const WrenchArgs<WRENCH>& wr) {
+    if (model->num_dof == model->num_bodies - 1 && model->num_bodies > 2)  // one revolute joint per body (robots; one shape)
+        return sim_launch_jt<STEP, PHC_JT_REVOLUTE, false, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+    if constexpr (!WRENCH)
+        if (model->num_shapes > 1 && sim->env_shape != nullptr)   // per-env body shapes (SMPL family)
+            return sim_launch_jt<STEP, PHC_JT_SPHERICAL, true, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+    sim_launch_jt<STEP, PHC_JT_SPHERICAL, false, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+}
+
+static inline int32_t launch_status() {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int32_t)e;
 }

@@ -1,6 +1,6 @@
 """External body wrenches (phc_sim_step_wrench) and the push schedule (`+perturb.*`) on a machine without a GPU.
 
-The stepper checks run through tests/wrench_hostemu_shim.cpp: the per-lane functions of phc_amd/csrc/phc_aba.h in the phase sequence of the kernel, with the
+The stepper checks run through oracle/hostemu's emu_sim_step_wrench: the per-lane functions of phc_amd/csrc/phc_aba.h in the phase sequence of the kernel, with the
 wrench handed to aba_body_init as the kernel's WRENCH instantiations hand it over -- at single precision and at double precision (the exact-arithmetic statement of
 the same recursion).  Each physical statement is checked at 1e-9 between two fp64 runs and, for the fp32 run against that fp64 run, at the tolerances the fp32
 stepper is held to against its references everywhere else (wrench_util.assert_standing)."""
@@ -27,7 +27,8 @@ def h1():
 @pytest.mark.parametrize("f64", [False, True], ids=["fp32", "fp64"])
 @pytest.mark.parametrize("robot", ["smpl_humanoid", "h1_humanoid", "g1_humanoid"])
 def test_null_wrench_is_the_host_emulation_bit_for_bit(robot, f64):
-    """Without a wrench (null pointers, and a wrench with wrench_sim_calls = 0) the shim IS oracle/hostemu's emu_sim_step: same bits in every output."""
+    """Without a wrench (null pointers, and a wrench with wrench_sim_calls = 0) emu_sim_step_wrench takes the plain route: it IS
+    oracle/hostemu's emu_sim_step, same bits in every output."""
     model = wu.load(robot)
     if model.all_spherical:
         root, dof, target = wu.smpl_state(model, 2, "ground", seed=1)

@@ -1,5 +1,5 @@
 """-m gpu: phc_sim_step_wrench -- the WRENCH instantiations of k_sim_step -- through the C ABI against the double-precision host statement of the same recursion
-(tests/wrench_hostemu_shim.cpp), the push schedule's plumbing in HumanoidIm, and the evaluation sweep under pushes.  States, wrenches and tolerances are those of
+(emu_sim_step_wrench of oracle/hostemu/hostemu64.cpp), the push schedule's plumbing in HumanoidIm, and the evaluation sweep under pushes.  States, wrenches and tolerances are those of
 tests/test_ext_wrench_cpu.py (tests/wrench_util.py)."""
 import numpy as np
 import pytest

@@ -1,43 +1,15 @@
-"""TEST INFRASTRUCTURE for the external-wrench tests (tests/test_ext_wrench_cpu.py, tests/test_ext_wrench_gpu.py): builds tests/wrench_hostemu_shim.cpp -- the host
-statement of phc_sim_step_wrench -- at single and at double precision, runs it, and holds the cases (states and wrenches) both test files use.
+"""TEST INFRASTRUCTURE for the external-wrench tests (tests/test_ext_wrench_cpu.py, tests/test_ext_wrench_gpu.py): runs the host statement of phc_sim_step_wrench
+-- oracle/hostemu's emu_sim_step_wrench -- at single and at double precision, and holds the cases (states and wrenches) both test files use.
 
 Forces stay at or below 300 N and torques at or below 50 N m, so that body speeds stay at a few m/s and the fp32 recursion stays inside the tolerances the
 stepper is held to everywhere else (tests/test_dynamics.py::check_step_against: positions 3e-4, velocities 3e-3 / rtol 1e-3; rigid contact 5e-4 and 1e-2)."""
-import atexit
-import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
-
 import numpy as np
 
 import dyn_oracle as do
 import hostemu_util as hu
-from phc_amd import _lib as L
 from phc_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-_SHIMS = {}
-_TMP = None
-
-
-def shim(f64):
-    """ctypes handle of the shim, built on first use (fp32: the structs of phc_amd/_lib.py; fp64: hostemu_util's `*64` mirrors)."""
-    global _TMP
-    if f64 not in _SHIMS:
-        if _TMP is None:
-            _TMP = tempfile.mkdtemp(prefix="wrench_shim_")
-            atexit.register(shutil.rmtree, _TMP, True)
-        so = os.path.join(_TMP, "wrench_shim64.so" if f64 else "wrench_shim32.so")
-        subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"] + (["-DWRENCH_SHIM_F64"] if f64 else []) +
-                       [os.path.join(ROOT, "tests", "wrench_hostemu_shim.cpp"), "-o", so], check=True)
-        lib = C.CDLL(so)
-        M, P_, S = (hu.Model64, hu.SimParams64, hu.SimState64) if f64 else (L.Model, L.SimParams, L.SimState)
-        lib.wrench_sim_step.argtypes = [C.POINTER(M), C.POINTER(P_), C.POINTER(S)] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
-        _SHIMS[f64] = lib
-    return _SHIMS[f64]
 
 
 def load(name):
@@ -51,33 +23,10 @@ def params(**kw):
 
 
 def host_step(model, prm, root, dof, target, num_sim_calls=2, force=None, torque=None, wrench_sim_calls=0, f64=False, gravity_z=None, reference=False):
-    """One launch on the host.  `reference`: through oracle/hostemu's emu_sim_step (no wrench) instead of the shim.  `gravity_z` (fp64 only): overrides the
-    parameter struct's value at full double precision.  -> dict(root, dof, rbs, cf, df) of arrays of the build's precision."""
-    T = np.float64 if f64 else F
-    ints, floats = model.pack(1.0, 1.0, float_dtype=T)
-    ms = abi.model_struct(ints, floats, model.num_bodies, model.num_dof, model.max_level, len(model.contact_body))
-    n, nb, nd = np.asarray(root).shape[0], model.num_bodies, model.num_dof
-    a = dict(root=np.array(root, dtype=T, order="C"), dof=np.array(dof, dtype=T, order="C"), rbs=np.zeros((n, nb, 13), T), cf=np.zeros((n, nb, 3), T),
-             df=np.zeros((n, nd), T), pd=np.array(target, dtype=T, order="C"))
-    sim = abi.sim_state_struct(n, a["root"], a["dof"], a["rbs"], a["cf"], a["df"], a["pd"])
-    p = prm
-    if f64:
-        ms, sim, p = hu._to64(ms, hu.Model64), hu._to64(sim, hu.SimState64), hu._to64(prm, hu.SimParams64)
-        if gravity_z is not None:
-            p.gravity_z = float(gravity_z)
-    else:
-        assert gravity_z is None
-    fo = None if force is None else np.array(force, dtype=T, order="C")
-    to = None if torque is None else np.array(torque, dtype=T, order="C")
-    if reference:
-        assert fo is None and to is None
-        rc = (hu.emu64() if f64 else hu.emu()).emu_sim_step(C.byref(ms), C.byref(p), C.byref(sim), None, None, None, None, int(num_sim_calls), 1)
-    else:
-        rc = shim(f64).wrench_sim_step(C.byref(ms), C.byref(p), C.byref(sim), None, None, None, None, int(num_sim_calls), abi.ptr(fo), abi.ptr(to),
-                                       int(wrench_sim_calls))
-    assert rc == 0, rc
-    a["floats"] = floats
-    return a
+    """One launch on the host.  `reference`: through oracle/hostemu's emu_sim_step (no wrench) instead of its emu_sim_step_wrench.  `gravity_z` (fp64 only):
+    overrides the parameter struct's value at full double precision.  -> dict(root, dof, rbs, cf, df) of arrays of the build's precision."""
+    return hu.host_sim_step(model, prm, root, dof, target, num_sim_calls, f64=f64, force=force, torque=torque,
+                            wrench_sim_calls=None if reference else wrench_sim_calls, gravity_z=gravity_z)
 
 
 def body_mass(model, f64=True):
