@@ -638,6 +638,45 @@ typedef struct {
 } phc_eval_args_t;
 int32_t phc_eval_accumulate(const phc_motion_lib_t* lib, const phc_eval_args_t* args /* host */, void* stream);
 
+/* Push schedule on the device (csrc/phc_push.hip, per-lane code csrc/phc_push.h; an addition to ABI 37, which stays 37): one launch is one
+ * `advance()` of the schedule of phc_amd/perturb.py -- all state and all random draws live on the device, so a captured launch moves on with
+ * every replay.  One lane per env, 256-thread blocks.  Per env i, with k = k[i] the env's own launch count:
+ *   u[0..4] = push_draws(key, env_offset + i, k): pause, magnitude, azimuth, height, body -- counter-based hashes, nothing is kept between launches;
+ *   reset   = k == 0 (the schedule's first step) or progress_buf[i] == 0 (the env was reset since the last step): the running push ends and
+ *             countdown = pause = pause_lo + min(floor(u[0] (pause_hi - pause_lo + 1)), pause_hi - pause_lo);
+ *   a push starts when remaining == 0 && countdown <= 0: remaining = duration, started[i] += 1, and row bodies[min(floor(u[4] num_listed),
+ *             num_listed - 1)] of force[i] becomes (force_lo + u[1] (force_hi - force_lo)) d with d = (cos az, sin az, 0), az = 2 pi u[2]
+ *             (direction 0) or d uniform on the sphere, z = 2 u[3] - 1 (direction 1);
+ *   while remaining > 0 the row keeps that value; in the first launch after the push's last step (or at a reset) the row is cleared.  A launch
+ *             writes at most two rows of force[i] (the cleared one and the new one) and no other element: the buffer starts as zeros;
+ *   then remaining = max(remaining - 1, 0), countdown = pause where the push's last step was this one, countdown - 1 while no push runs,
+ *             k[i] += 1.  body[i] is the row that holds a force, -1 for none.
+ * After the launch `force` holds what acts during this env step (phc_sim_step_wrench reads it).  The integer state is bit-equal to the host build
+ * of phc_push.h; the force differs by the sinf / cosf / sqrtf implementations only.
+ * PHC_EINVAL before any device work for: a null args / bodies / state / force pointer, num_envs < 0, num_bodies outside [1, PHC_MAX_BODIES],
+ * num_listed outside [1, PHC_MAX_BODIES], pause_lo < 0, pause_hi < pause_lo or > 2^24, duration < 1, a direction other than 0 / 1, a force range that is
+ * not 0 <= force_lo <= force_hi < inf, env_offset < 0 or env_offset + num_envs > 2^32.  The entries of `bodies` are device memory: the caller
+ * guarantees 0 <= bodies[j] < num_bodies (phc_amd/perturb.py checks them before the upload).  num_envs == 0 returns 0 without a launch. */
+typedef struct {
+    int32_t num_envs, num_bodies;             /* N, NB */
+    int32_t num_listed;                       /* entries of `bodies` */
+    int32_t pause_lo, pause_hi;               /* env steps between the end of a push and the next one */
+    int32_t duration;                         /* env steps a push lasts */
+    int32_t direction;                        /* 0 = horizontal, 1 = any */
+    float force_lo, force_hi;                 /* newtons */
+    uint64_t key;                             /* stream key (the caller folds its seed into it) */
+    int64_t env_offset;                       /* global index of env 0: the ranks of one run draw disjoint streams from one key */
+    const int32_t* bodies;                    /* device [num_listed] */
+    const int64_t* progress_buf;              /* [N]; nullable = no env was reset */
+    int32_t* remaining;                       /* [N] env steps the running push still lasts */
+    int32_t* countdown;                       /* [N] force-free env steps before the next push */
+    int32_t* body;                            /* [N] the row of force[i] that is non-zero, or -1 */
+    int32_t* k;                               /* [N] launches this env has seen (the draw counter) */
+    int32_t* started;                         /* [N] pushes started; their sum is the schedule's push count */
+    float* force;                             /* [N, NB, 3] */
+} phc_push_args_t;
+int32_t phc_push_advance(const phc_push_args_t* args /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,12 @@ class EvalArgs(C.Structure):
                 ("failed", c_p), ("status", c_p), ("mpjpe_step", c_p), ("gt_out", c_p)]
 
 
+class PushArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("num_listed", c_i32), ("pause_lo", c_i32), ("pause_hi", c_i32), ("duration", c_i32),
+                ("direction", c_i32), ("force_lo", c_f), ("force_hi", c_f), ("key", C.c_uint64), ("env_offset", c_i64), ("bodies", c_p),
+                ("progress_buf", c_p), ("remaining", c_p), ("countdown", c_p), ("body", c_p), ("k", c_p), ("started", c_p), ("force", c_p)]
+
+
 P = C.POINTER
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
@@ -156,6 +162,7 @@ _SIGNATURES = {
     "phc_ppo_loss": ([c_p, c_p, c_i32] + [c_p] * 9 + [c_i64, c_i32, P(PpoParams), c_p, c_p, c_p, c_p, c_p], c_i32),
     "phc_render": ([P(RenderScene), P(Camera), c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p], c_i32),
     "phc_eval_accumulate": ([P(MotionLib), P(EvalArgs), c_p], c_i32),
+    "phc_push_advance": ([P(PushArgs), c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

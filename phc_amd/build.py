@@ -17,10 +17,12 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #   matrix-core kernels (phc_gemm.hip): no contraction either (the fp32 slab and bias sums are plain adds in a fixed order).
 #   renderer (phc_render.hip, off the training path): IEEE fp32 (no fast-math): its error bound assumes correctly rounded sqrt / division.
 #   evaluation metrics (phc_eval.hip): no contraction -- its reference positions are bit-equal to phc_motion_state's.
+#   push schedule (phc_push.hip): no contraction, no fast-math -- its integer state is bit-equal to the host build of phc_push.h.
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"],
-           "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_eval.h", "phc_group.h", os.path.join("..", "..", "include", "phc_amd.h")]
+           "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
+           "phc_push.hip": ["-ffp-contract=off"]}
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

@@ -9,6 +9,7 @@
 #include "phc_aba.h"  // model table accessors (k_fk)
 #include "phc_im.h"
 #include "phc_group.h"  // group_sum / group_or
+#include "phc_rng.h"    // hash_u01 / splitmix64
 
 using namespace phc;
 
@@ -90,21 +91,7 @@ __global__ __launch_bounds__(256) void k_im_reset_from_state(phc_model_t model, 
 
 // Reset of a list of envs.  One lane group per (env, AMP history frame k): group k == 0 also imposes the state
 // and recomputes the observations.  blockDim = 256.
-// counter-based uniform in [0,1): the host folds (seed, counter) into one 64-bit stream key (splitmix64); per env a 32-bit
-// avalanche hash (murmur3 finaliser rounds) of the env id under that key, top 24 bits -> float like torch.rand
-__device__ __forceinline__ float hash_u01(uint64_t key, uint32_t env) {
-    uint32_t x = env * 0x9E3779B1u ^ (uint32_t)key;
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    x += (uint32_t)(key >> 32);
-    x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12; x *= 0x297A2D39u; x ^= x >> 15;
-    return (float)(x >> 8) * (1.0f / 16777216.0f);
-}
-__host__ __device__ static inline uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (start times: counter-based uniforms, hash_u01 / splitmix64 of phc_rng.h)
 
 #ifdef PHC_SIM_PROFILE   // one lane group's timeline through the reset kernel (scripts/probes/reset_timeline.py; the product library has none of this)
 __device__ unsigned long long g_phc_rtl[64];

@@ -451,8 +451,10 @@ class HumanoidIm:
         pcfg = cfg.get("perturb", None)
         if pcfg:
             self._check_wrench_supported("perturb")
-            from ...perturb import PushSchedule
-            self._push = PushSchedule(pcfg, N, list(self._body_names), self.dt, dev, default_seed=int(cfg.get("seed", 0)))
+            from ...perturb import make_schedule
+            # (`+perturb.rng=device`: one launch per step, capturable; the ranks of a multi-GPU run draw disjoint streams from one seed)
+            self._push = make_schedule(pcfg, N, list(self._body_names), self.dt, dev, default_seed=int(cfg.get("seed", 0)),
+                                       env_offset=int(cfg.get("rank", os.environ.get("RANK", 0))) * N)
 
         # ---- action scaling (A1) + freeze masks (humanoid.py:1331-1409,1549-1554) ----
         self.dof_limits_lower, self.dof_limits_upper = (torch.from_numpy(x).to(dev) for x in self.model.dof_limits())
@@ -826,7 +828,7 @@ class HumanoidIm:
         if self._occl_training:   # humanoid_im.py:1112-1113
             self._update_occl_training()
         if self._push is not None:   # (an env reset since the last step has progress 0: its push ends, a new pause is drawn)
-            self._push.advance(self.progress_buf == 0)
+            self._push.advance(self.progress_buf if self._push.capturable else self.progress_buf == 0)
 
     def _update_occl_training(self):
         """humanoid_im.py:1081-1092: occlusion spans of 30-59 steps start with probability occl_training_prob per tracked body and step (never the
@@ -984,11 +986,23 @@ class HumanoidIm:
         """The counters behind the device-side start-time draws of `reset_done()` (phc_im_buffers_t.reset_rng_counter, advanced by every
         post-physics launch, and the host call counter): saved with a checkpoint (IMAmpAgent.get_full_state_weights, key `env_state`) so that a
         resumed run continues the draw sequence instead of repeating it from the top."""
-        return {"reset_rng_counter": int(self._reset_rng_dev.item()), "reset_counter": int(self._reset_counter)}
+        state = {"reset_rng_counter": int(self._reset_rng_dev.item()), "reset_counter": int(self._reset_counter)}
+        if hasattr(self._push, "state_dict"):   # `+perturb.rng=device`: a resumed run continues its pushes
+            state["push_schedule"] = self._push.state_dict()
+        return state
 
     def set_env_rng_state(self, state):
         self._reset_rng_dev.fill_(int(state.get("reset_rng_counter", 0)))
         self._reset_counter = int(state.get("reset_counter", 0))
+        # the push schedule continues only where a training run with the same envs resumes: play and the sweep (flags.test) run the schedule they were
+        # configured with, another env count has no state to continue, and a checkpoint without the key starts the schedule afresh, as before
+        saved = state.get("push_schedule")
+        if saved is not None and hasattr(self._push, "load_state_dict") and not flags.test:
+            if self._push.fits(saved):
+                self._push.load_state_dict(saved)
+            else:
+                print(f"[phc_amd] push schedule state not restored: the checkpoint's is for {tuple(saved['state'].shape)[-1]} envs, this task has "
+                      f"{self.num_envs}; the schedule starts afresh", flush=True)
 
     def whole_step_capturable(self):
         """True when reset_done() + step() consist of launches and host bookkeeping only (no host-side random draws or syncs between them), so that

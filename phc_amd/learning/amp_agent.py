@@ -1065,6 +1065,8 @@ class IMAmpAgent:
         self.obs = self.env_reset()
         self._init_amp_demo_buf()
 
+    _push_seen = 0   # the schedule's push count at the last read (`perturb/pushes` is the difference per epoch)
+
     def train_epoch(self):
         self.epoch_num += 1
         self.pre_epoch(self.epoch_num)
@@ -1110,6 +1112,10 @@ class IMAmpAgent:
         info.update(play_time=t1 - t0, update_time=t2 - t1, total_time=t2 - t0, mean_task_reward=rs[0], mean_disc_reward=rs[1], disc_reward_std=rs[2],
                     mean_mb_reward=rs[3], mean_return=rs[4], reward_raw=batch["reward_raw"].tolist(),
                     step_fps=self.batch_size / (t1 - t0), total_fps=self.batch_size / (t2 - t0))  # common_agent.py:134-138
+        push = getattr(self.task, "_push", None)
+        if push is not None:   # `+perturb.*` (train() admits the device schedule only): pushes started during this epoch's rollout in THIS rank's envs -- one scalar read, no reduction over ranks
+            total = int(push.pushes)
+            info["perturb/pushes"], self._push_seen = total - self._push_seen, total
         if self._trace is not None:   # `+learning.params.config.trace_minibatches=True`: every optimizer step's scalars, in order (a diagnostic)
             tr = torch.stack(self._trace).cpu() if self._trace else torch.zeros(0)
             info["minibatch_trace"] = {k: tr[:, j].tolist() for j, k in enumerate(self.INFO_KEYS)} if tr.numel() else {}
@@ -1130,7 +1136,7 @@ class IMAmpAgent:
                "disc/reward_std": info["disc_reward_std"], "rewards/returns": info["mean_return"],
                "rewards/mb_rewards": info["mean_mb_reward"], "rewards/body_pos": raw[0], "rewards/body_rot": raw[1], "rewards/lin_vel": raw[2], "rewards/ang_vel": raw[3],
                "rewards/power": raw[4]}
-        out.update({k: v for k, v in info.items() if k.startswith("eval/")})
+        out.update({k: v for k, v in info.items() if k.startswith(("eval/", "perturb/"))})
         return {k: float(v) for k, v in out.items()}
 
     def _log_train_info(self, scalars, output_dir):
@@ -1158,10 +1164,14 @@ class IMAmpAgent:
         `Humanoid.pth` every min(50, save_best_after) epochs; every `save_frequency` epochs (save_intermediate) also
         `Humanoid_{epoch:08d}.pth` and the evaluation sweep `eval()`, which re-weights the clip sampling (auto-PMCP, im_amp.py:126-132)
         and writes `failed_{epoch:010d}.pkl`."""
-        if getattr(self.task, "_push", None) is not None:
+        push = getattr(self.task, "_push", None)
+        if push is not None and not getattr(push, "capturable", False):
             # the captured rollout graph freezes the launch sequence and the state of the schedule's generator
-            raise NotImplementedError("training under a push schedule (+perturb.*) is not built: pushes act in play (test=True) and in the evaluation sweep")
+            raise NotImplementedError("training under a torch-generator push schedule (+perturb.rng=torch, the default) is not built: it pushes in play (test=True) "
+                                      "and in the evaluation sweep; +perturb.rng=device is the schedule that trains")
         self.init_train()
+        if push is not None:
+            self._push_seen = int(push.pushes)
         c = self.config
         save_freq, save_best_after = int(c.get("save_frequency", 0)), int(c.get("save_best_after", 100))
         save_intermediate = bool(c.get("save_intermediate", False))
@@ -1170,7 +1180,8 @@ class IMAmpAgent:
             info = self.train_epoch()
             if self.rank == 0 and log is not None:
                 log(f"epoch {self.epoch_num}: total_fps {info['total_fps']:.0f} step_fps {info['step_fps']:.0f} task_r {info['mean_task_reward']:.4f} "
-                    f"disc_r {info['mean_disc_reward']:.4f} a_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f}")
+                    f"disc_r {info['mean_disc_reward']:.4f} a_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f}"
+                    + (f" perturb/pushes {info['perturb/pushes']}" if "perturb/pushes" in info else ""))
             if output_dir is not None and save_freq > 0:
                 if self.epoch_num % min(50, save_best_after) == 0 and self.rank == 0:
                     os.makedirs(output_dir, exist_ok=True)
@@ -1182,6 +1193,8 @@ class IMAmpAgent:
                     if hasattr(self.task, "_motion_lib") and hasattr(self.task, "_termination_distances"):
                         eval_info, _ = self.eval(output_dir=output_dir, log=log)
                         info.update(eval_info)
+                        if push is not None:   # (the sweep ran on the same schedule: its pushes are in `perturb_pushes`, not in the next epoch's count)
+                            self._push_seen = int(push.pushes)
             if output_dir is not None and self.rank == 0:
                 self._log_train_info(self.assemble_train_info(info), output_dir)
         return info
