@@ -8,7 +8,7 @@
 #include <omp.h>
 #include "../../phc_amd/csrc/phc_aba.h"
 #include "../../phc_amd/csrc/phc_im.h"
-#include "../../phc_amd/csrc/phc_sim_check.h"
+#include "../../phc_amd/csrc/phc_im_check.h"   // (and phc_sim_check.h): the refusals of the entry points, returned first by every function here
 
 using namespace phc;
 
@@ -107,6 +107,25 @@ static int emu_sim_step_t(const phc_model_t* model_all, const phc_sim_params_t* 
     return 0;
 }
 
+// Both reset launches (k_im_reset<RNG>): row r of the grid settles its env and start time once (the reset pick of phc_im.h; the device repeats it in every group
+// of the row).  The env's AMP history groups run before its state group, and the lanes of that group in descending order: lane 0 writes what the others read.
+template <bool RNG>
+static void emu_reset_groups(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
+                             const phc_im_buffers_t* buf, int n, const int64_t* env_ids, const float* phase, int start_at_zero, uint64_t key) {
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int r = 0; r < n; ++r) {
+        if (!im_reset_pick_live<RNG>(*buf, r, 0, 0, n, env_ids)) continue;
+        const int64_t env = im_reset_pick_env<RNG>(*buf, r, env_ids);   // (NULL motion-id table = identity, as on the device: ABI 33)
+        const float t = im_reset_pick_time<RNG>(*buf, *lib, env, r, phase, start_at_zero, key);
+        for (int k = 0; k < prm->num_amp_obs_steps; ++k)
+            for (int lane = 0; lane < PHC_MAX_BODIES; ++lane) {
+                if (prm->amp_ref_table) im_reset_amp_table_lane(*lib, *prm, *buf, model->num_bodies, env, lane, PHC_MAX_BODIES, t, k);
+                else im_reset_amp_lane(*lib, *prm, *buf, model->num_bodies, env, lane, t, k);
+            }
+        for (int lane = PHC_MAX_BODIES - 1; lane >= 0; --lane) im_reset_lane(*model, *lib, *prm, *sim, *buf, env, lane, t, env_ids != nullptr);
+    }
+}
+
 extern "C" {
 
 void emu_set_threads(int n) { omp_set_num_threads(n > 0 ? n : 1); }
@@ -115,35 +134,10 @@ int emu_max_threads(void) { return omp_get_max_threads(); }
 int emu_motion_state(const phc_motion_lib_t* lib, int n, const int64_t* ids, const float* times, const float* offset,
                      float* rg_pos, float* rb_rot, float* body_vel, float* body_ang_vel, float* dof_pos, float* dof_vel,
                      int64_t* idx0, int64_t* idx1, float* blend, float* rg_pos_ext, float* rb_rot_ext) {
-    const int nb = lib->num_bodies, ne = lib->num_ext_bodies;
-    for (int64_t i = 0; i < n; ++i) {
-        FrameRef fr = frame_ref(*lib, ids[i], times[i]);
-        if (idx0) idx0[i] = fr.idx0;
-        if (idx1) idx1[i] = fr.idx1;
-        if (blend) blend[i] = fr.blend;
-        for (int e = 0; e < ne; ++e) {
-            V3 p; Q4 q;
-            ref_body_ext(*lib, fr, e, &p, &q);
-            if (offset) p += ld3(offset + i * 3);
-            if (rg_pos_ext) st3(rg_pos_ext + (i * ne + e) * 3, p);
-            if (rb_rot_ext) st4(rb_rot_ext + (i * ne + e) * 4, q);
-        }
-        for (int j = 0; j < nb; ++j) {
-            BodyState s = ref_body(*lib, fr, j);
-            if (offset) s.pos += ld3(offset + i * 3);
-            if (rg_pos) st3(rg_pos + (i * nb + j) * 3, s.pos);
-            if (rb_rot) st4(rb_rot + (i * nb + j) * 4, s.rot);
-            if (body_vel) st3(body_vel + (i * nb + j) * 3, s.vel);
-            if (body_ang_vel) st3(body_ang_vel + (i * nb + j) * 3, s.angvel);
-            if (j >= 1 && (dof_pos || dof_vel)) {
-                V3 dp, dv;
-                ref_joint(*lib, fr, j, &dp, &dv);
-                const int dpj = lib->dofs_per_joint == 1 ? 1 : 3;
-                if (dof_pos) st_joint(dof_pos + (i * (nb - 1) + (j - 1)) * dpj, dpj, dp);
-                if (dof_vel) st_joint(dof_vel + (i * (nb - 1) + (j - 1)) * dpj, dpj, dv);
-            }
-        }
-    }
+    if (const int rc = check_motion_state(lib, n)) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        for (int lane = 0; lane < PHC_MAX_BODIES; ++lane)
+            motion_state_lane(*lib, i, lane, ids, times, offset, rg_pos, rb_rot, body_vel, body_ang_vel, dof_pos, dof_vel, idx0, idx1, blend, rg_pos_ext, rb_rot_ext);
     return 0;
 }
 
@@ -154,6 +148,7 @@ int emu_sample_time_interval(const phc_motion_lib_t* lib, int n, const int64_t* 
 
 int emu_im_post_physics(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm,
                         const phc_sim_state_t* sim, const phc_im_buffers_t* buf) {
+    if (const int rc = check_im_post_physics(model, lib, prm, sim, buf)) return rc;
 #pragma omp parallel for schedule(static)
     for (int64_t env = 0; env < sim->num_envs; ++env) {
         const int64_t progress = buf->progress_buf[env] + 1;
@@ -180,6 +175,7 @@ int emu_im_post_physics(const phc_model_t* model, const phc_motion_lib_t* lib, c
 
 int emu_im_reset_from_state(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
                             const phc_im_buffers_t* buf, int num_reset, const int64_t* env_ids, int fill_history) {
+    if (const int rc = check_im_reset_from_state(model, lib, prm, sim, buf, num_reset, env_ids)) return rc;
     for (int r = 0; r < num_reset; ++r)
         for (int lane = PHC_MAX_BODIES - 1; lane >= 0; --lane) im_reset_from_state_lane(*model, *lib, *prm, *sim, *buf, env_ids[r], lane, fill_history);
     return 0;
@@ -187,24 +183,24 @@ int emu_im_reset_from_state(const phc_model_t* model, const phc_motion_lib_t* li
 
 int emu_im_reset(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
                  const phc_im_buffers_t* buf, int num_reset, const int64_t* env_ids, const float* phase, int start_at_zero) {
-#pragma omp parallel for schedule(dynamic, 8)
-    for (int r = 0; r < num_reset; ++r) {
-        const int64_t env = env_ids ? env_ids[r] : r;
-        if (!env_ids && buf->reset_buf[env] == 0) continue;
-        const int64_t mid = motion_id_of(*buf, env);   // (NULL table = identity, as on the device: ABI 33)
-        const float t = start_at_zero ? 0.f : sample_time_interval(*lib, mid, phase[r]);
-        for (int k = 0; k < prm->num_amp_obs_steps; ++k)
-            for (int lane = 0; lane < PHC_MAX_BODIES; ++lane) {
-                if (prm->amp_ref_table) im_reset_amp_table_lane(*lib, *prm, *buf, model->num_bodies, env, lane, PHC_MAX_BODIES, t, k);
-                else im_reset_amp_lane(*lib, *prm, *buf, model->num_bodies, env, lane, t, k);
-            }
-        for (int lane = PHC_MAX_BODIES - 1; lane >= 0; --lane) im_reset_lane(*model, *lib, *prm, *sim, *buf, env, lane, t, true);
-    }
+    if (const int rc = check_im_reset(model, lib, prm, sim, buf, num_reset, phase, start_at_zero)) return rc;
+    emu_reset_groups<false>(model, lib, prm, sim, buf, num_reset, env_ids, phase, start_at_zero, 0ull);
+    return 0;
+}
+
+// phc_im_reset_done: the device-built list of finished envs (buf->reset_list) or, without one, the masked sweep; start times drawn per env from (seed, counter)
+int emu_im_reset_done(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
+                      const phc_im_buffers_t* buf, uint64_t seed, uint64_t counter, int start_at_zero) {
+    const int rc = check_im_reset_done(model, lib, prm, sim, buf);
+    if (rc || sim->num_envs == 0) return rc;
+    const int n = buf->reset_list ? buf->reset_sublist_cap * PHC_RESET_SUBLISTS : sim->num_envs;   // groups, as launched
+    emu_reset_groups<true>(model, lib, prm, sim, buf, n, nullptr, nullptr, start_at_zero, im_reset_done_key(*buf, seed, counter));
     return 0;
 }
 
 int emu_amp_obs_demo(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, int n,
                      const int64_t* ids, const float* times0, float* out) {
+    if (const int rc = check_amp_obs_demo(model, lib, prm, n)) return rc;
     const int S = prm->num_amp_obs_steps, A = prm->num_amp_obs_per_step;
     for (int64_t g = 0; g < (int64_t)n * S; ++g) {
         const int64_t i = g / S;
@@ -220,6 +216,7 @@ int emu_amp_obs_demo(const phc_model_t* model, const phc_motion_lib_t* lib, cons
 // phc_amp_ref_table: row f = the AMP observation of the lookup (f, next_frame[f], blend 0)
 int emu_amp_ref_table(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, int64_t num_frames,
                       const int64_t* next_frame, float* table) {
+    if (const int rc = check_amp_ref_table(model, lib, prm, num_frames, next_frame, table)) return rc;
     const int W = prm->num_amp_obs_per_step - prm->num_amp_obs_extra;
 #pragma omp parallel for schedule(static)
     for (int64_t f = 0; f < num_frames; ++f) {
@@ -254,8 +251,7 @@ int emu_sim_step_wrench(const phc_model_t* model, const phc_sim_params_t* prm, c
                         int wrench_sim_calls) {
     const int calls = wrench_sim_calls < 0 ? 0 : (wrench_sim_calls > num_sim_calls ? num_sim_calls : wrench_sim_calls);
     if ((!ext_force && !ext_torque) || calls == 0) return emu_sim_step(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, 1);
-    const int rc = check_sim_step_wrench(model, prm, sim, actions, pd_off, pd_scale, num_sim_calls);
-    if (rc) return rc;
+    if (const int rc = check_sim_step_wrench(model, prm, sim, actions, pd_off, pd_scale, num_sim_calls)) return rc;
     return emu_sim_step_jt(model, prm, sim, actions, pd_off, pd_scale, freeze, num_sim_calls, 1, ext_force, ext_torque, calls * prm->substeps);
 }
 

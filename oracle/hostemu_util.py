@@ -48,6 +48,7 @@ def emu():
         lib.emu_sample_time_interval.argtypes = [PS(L.MotionLib), i32, vp, vp, vp]
         lib.emu_im_post_physics.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), PS(L.SimState), PS(L.ImBuffers)]
         lib.emu_im_reset.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), PS(L.SimState), PS(L.ImBuffers), i32, vp, vp, i32]
+        lib.emu_im_reset_done.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), PS(L.SimState), PS(L.ImBuffers), C.c_uint64, C.c_uint64, i32]
         lib.emu_im_reset_from_state.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), PS(L.SimState), PS(L.ImBuffers), i32, vp, i32]
         lib.emu_amp_obs_demo.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), i32, vp, vp, vp]
         lib.emu_amp_ref_table.argtypes = [PS(L.Model), PS(L.MotionLib), PS(L.ImParams), C.c_int64, vp, vp]
@@ -58,7 +59,7 @@ def emu():
 
 
 def P(s):
-    return C.byref(s)
+    return None if s is None else C.byref(s)   # (None: a null struct pointer, for the refusal tests)
 
 
 def np_model(name="smpl_humanoid", kp_scale=1.0, kd_scale=1.0):

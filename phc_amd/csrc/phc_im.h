@@ -3,6 +3,7 @@
 // code lane-by-lane on the CPU.  Reference call sites are cited at each step.
 #pragma once
 #include "phc_task.h"
+#include "phc_rng.h"   // hash_u01 / splitmix64: the start-time draws of the reset launch
 
 namespace phc {
 
@@ -398,6 +399,50 @@ PHC_HD void im_post_finalize(const phc_motion_lib_t& lib, const phc_im_params_t&
         buf.motion_start_times_offset[env] = c.start_off;
         st3(buf.global_offset + env * 3, c.goff);
     }
+}
+
+// The reset pick: what a lane group of the reset launch settles before its lane work -- whether row r of the grid has an env at all, which env, and the
+// start time it imposes.  One group per (r, k); k and lane only say who zeroes a counter.
+//   RNG = false (phc_im_reset): entry r of `env_ids`, or -- env_ids == NULL, the masked sweep -- env r if its reset flag is set; t from phase[r].
+//   RNG = true (phc_im_reset_done): the masked sweep, or the device-built list of finished envs (phc_im_buffers_t.reset_list); t from a
+//   counter-keyed draw per env (phc_rng.h), so list and sweep impose the same times.
+// Three questions, three functions, so that the kernel leaves on the first answer alone: a flag returned beside the env and the time stays a branch.
+template <bool RNG>
+PHC_HD int64_t im_reset_pick_env(const phc_im_buffers_t& buf, int64_t r, const int64_t* env_ids) {
+    if (RNG && buf.reset_list) return buf.reset_list[((int)r & (PHC_RESET_SUBLISTS - 1)) * buf.reset_sublist_cap + ((int)r >> 4)];
+    return env_ids ? env_ids[r] : r;
+}
+template <bool RNG>
+PHC_HD bool im_reset_pick_live(const phc_im_buffers_t& buf, int64_t r, int k, int lane, int num_reset, const int64_t* env_ids) {
+    if (RNG && buf.reset_list) {
+        // reset_done() on the device-built list of finished envs: dense wavefronts, blocks beyond the count leave at once
+        const int cap = buf.reset_sublist_cap, r32 = (int)r;
+        // group r works on entry r / 16 of sub-list r % 16: concurrently running wavefronts draw from all sub-lists (a sub-list holds
+        // envs of every 16th workgroup, whose clips sit at a fixed stride in HBM -- walking one sub-list at a time camps on channels)
+        const int sub = r32 & (PHC_RESET_SUBLISTS - 1), i = r32 >> 4;
+        if (r32 < PHC_RESET_SUBLISTS && k == 0 && lane == 0)   // next step's counters
+            buf.reset_count[(((buf.reset_slot + 1) % 3) * PHC_RESET_SUBLISTS + r32) * PHC_RESET_COUNT_STRIDE] = 0;
+        return !(i >= cap || i >= buf.reset_count[(buf.reset_slot * PHC_RESET_SUBLISTS + sub) * PHC_RESET_COUNT_STRIDE]);
+    }
+    if (r >= num_reset) return false;
+    // env_ids == NULL: masked mode over all envs (reset every env whose reset_buf is set) -- no host sync needed.
+    // The flag is NOT cleared here (other groups of the same env still read it).
+    return !(!env_ids && buf.reset_buf[im_reset_pick_env<RNG>(buf, r, env_ids)] == 0);
+}
+// _sample_ref_state (humanoid_im.py:1000-1023): StateInit.Random -> sample_time_interval; Start / flags.test -> 0
+// (start_at_zero with a null phase array is only legal in the RNG-free instantiation's list mode)
+template <bool RNG>
+PHC_HD float im_reset_pick_time(const phc_im_buffers_t& buf, const phc_motion_lib_t& lib, int64_t env, int64_t r, const float* phase, int start_at_zero,
+                                uint64_t rng_key) {
+    const int64_t mid = motion_id_of(buf, env);
+    // (device-side call counter, phc_im_buffers_t.reset_rng_counter: folded into the key so that a captured launch draws anew on every replay)
+    const uint64_t key = (RNG && buf.reset_rng_counter) ? splitmix64(rng_key ^ (*buf.reset_rng_counter * 0x9E6C63D0876A9A47ull)) : rng_key;
+    return start_at_zero ? 0.f : sample_time_interval(lib, mid, RNG ? hash_u01(key, (uint32_t)env) : phase[r]);
+}
+// the stream key phc_im_reset_done hands to the pick
+// (with a device-side call counter the host one stays out of the key: a captured launch and an eager one then draw the same numbers)
+PHC_HD uint64_t im_reset_done_key(const phc_im_buffers_t& buf, uint64_t seed, uint64_t counter) {
+    return splitmix64(splitmix64(seed) ^ ((buf.reset_rng_counter ? 0ull : counter) * 0xD1342543DE82EF95ull));
 }
 
 // Reset of one env, lane j: HumanoidIm._reset_envs (humanoid.py:585-621; humanoid_amp.py:378-398,508-528,

@@ -7,9 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "phc_aba.h"  // model table accessors (k_fk)
+#include <type_traits>
 #include "phc_im.h"
+#include "phc_im_check.h"  // what the entry points refuse
 #include "phc_group.h"  // group_sum / group_or
-#include "phc_rng.h"    // hash_u01 / splitmix64
 
 using namespace phc;
 
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void k_im_reset_from_state(phc_model_t model, 
 
 // Reset of a list of envs.  One lane group per (env, AMP history frame k): group k == 0 also imposes the state
 // and recomputes the observations.  blockDim = 256.
-// (start times: counter-based uniforms, hash_u01 / splitmix64 of phc_rng.h)
+// (which env and which start time: im_reset_pick, phc_im.h)
 
 #ifdef PHC_SIM_PROFILE   // one lane group's timeline through the reset kernel (scripts/probes/reset_timeline.py; the product library has none of this)
 __device__ unsigned long long g_phc_rtl[64];
@@ -125,31 +126,9 @@ __global__ __launch_bounds__(256) void k_im_reset(phc_model_t model, phc_motion_
     const bool rtl_on = (int)(r * 16 + k) == g_phc_rtl_group;
 #endif
     PHC_RTL(0)
-    int64_t env;
-    if (RNG && buf.reset_list) {
-        // reset_done() on the device-built list of finished envs: dense wavefronts, blocks beyond the count leave at once
-        const int cap = buf.reset_sublist_cap, r32 = (int)r;
-        // group r works on entry r / 16 of sub-list r % 16: concurrently running wavefronts draw from all sub-lists (a sub-list holds
-        // envs of every 16th workgroup, whose clips sit at a fixed stride in HBM -- walking one sub-list at a time camps on channels)
-        const int sub = r32 & (PHC_RESET_SUBLISTS - 1), i = r32 >> 4;
-        if (r32 < PHC_RESET_SUBLISTS && k == 0 && lane == 0)   // next step's counters
-            buf.reset_count[(((buf.reset_slot + 1) % 3) * PHC_RESET_SUBLISTS + r32) * PHC_RESET_COUNT_STRIDE] = 0;
-        if (i >= cap || i >= buf.reset_count[(buf.reset_slot * PHC_RESET_SUBLISTS + sub) * PHC_RESET_COUNT_STRIDE]) return;
-        env = buf.reset_list[sub * cap + i];
-    } else {
-        if (r >= num_reset) return;
-        // env_ids == NULL: masked mode over all envs (reset every env whose reset_buf is set) -- no host sync needed.
-        // The flag is NOT cleared here (other groups of the same env still read it).
-        env = env_ids ? env_ids[r] : r;
-        if (!env_ids && buf.reset_buf[env] == 0) return;
-    }
-    PHC_RTL(1)
-    const int64_t mid = motion_id_of(buf, env);
-    // _sample_ref_state (humanoid_im.py:1000-1023): StateInit.Random -> sample_time_interval; Start / flags.test -> 0
-    // (start_at_zero with a null phase array is only legal in the RNG-free instantiation's list mode)
-    // (device-side call counter, phc_im_buffers_t.reset_rng_counter: folded into the key so that a captured launch draws anew on every replay)
-    const uint64_t key = (RNG && buf.reset_rng_counter) ? splitmix64(rng_key ^ (*buf.reset_rng_counter * 0x9E6C63D0876A9A47ull)) : rng_key;
-    const float t = start_at_zero ? 0.f : sample_time_interval(lib, mid, RNG ? hash_u01(key, (uint32_t)env) : phase[r]);
+    if (!im_reset_pick_live<RNG>(buf, r, k, lane, num_reset, env_ids)) return;
+    const int64_t env = im_reset_pick_env<RNG>(buf, r, env_ids);
+    const float t = im_reset_pick_time<RNG>(buf, lib, env, r, phase, start_at_zero, rng_key);   // (PHC_RTL(1) stood inside the pick)
     PHC_RTL(2)
     if (k < 2) im_reset_lane(model, lib, prm, sim, buf, env, lane, t, env_ids != nullptr, 1 << k);
     PHC_RTL(3)
@@ -185,37 +164,7 @@ __global__ __launch_bounds__(256) void k_motion_state(phc_motion_lib_t lib, int 
     const int lane = threadIdx.x & (G - 1);
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
     if (i >= n) return;
-    const int nb = lib.num_bodies;
-    const FrameRef fr = frame_ref(lib, ids[i], times[i]);
-    if (lane == 0) {
-        if (idx0) idx0[i] = fr.idx0;
-        if (idx1) idx1[i] = fr.idx1;
-        if (blend) blend[i] = fr.blend;
-    }
-    if (lane >= nb) {
-        const int e = lane - nb, ne = lib.num_ext_bodies;
-        if (e < ne && (rg_pos_ext || rb_rot_ext)) {
-            V3 p; Q4 q;
-            ref_body_ext(lib, fr, e, &p, &q);
-            if (offset) p += ld3(offset + i * 3);
-            if (rg_pos_ext) st3(rg_pos_ext + (i * ne + e) * 3, p);
-            if (rb_rot_ext) st4(rb_rot_ext + (i * ne + e) * 4, q);
-        }
-        return;
-    }
-    BodyState s = ref_body(lib, fr, lane);
-    if (offset) s.pos += ld3(offset + i * 3);
-    if (rg_pos) st3(rg_pos + (i * nb + lane) * 3, s.pos);
-    if (rb_rot) st4(rb_rot + (i * nb + lane) * 4, s.rot);
-    if (body_vel) st3(body_vel + (i * nb + lane) * 3, s.vel);
-    if (body_ang_vel) st3(body_ang_vel + (i * nb + lane) * 3, s.angvel);
-    if (lane >= 1 && (dof_pos || dof_vel)) {
-        V3 dp, dv;
-        ref_joint(lib, fr, lane, &dp, &dv);
-        const int dpj = lib.dofs_per_joint == 1 ? 1 : 3;
-        if (dof_pos) st_joint(dof_pos + (i * (nb - 1) + (lane - 1)) * dpj, dpj, dp);
-        if (dof_vel) st_joint(dof_vel + (i * (nb - 1) + (lane - 1)) * dpj, dpj, dv);
-    }
+    motion_state_lane(lib, i, lane, ids, times, offset, rg_pos, rb_rot, body_vel, body_ang_vel, dof_pos, dof_vel, idx0, idx1, blend, rg_pos_ext, rb_rot_ext);
 }
 
 __global__ void k_sample_time_interval(phc_motion_lib_t lib, int n, const int64_t* __restrict__ ids,
@@ -281,6 +230,26 @@ static inline int env_blocks(int64_t groups, int lanes) { return (int)((groups *
 // lanes per env: 32 while the articulation (with its extended reference bodies) fits, else 64
 static inline int group_lanes(int num_bodies, int num_ext) { return num_bodies + num_ext > 32 ? 64 : 32; }
 
+// The launch chooser of the task kernels: the run-time pair (joint family, lanes per env) as compile-time constants.  `launch(dpj, g)` is a generic lambda that
+// names its kernel with them -- k<dpj, g>, or k<g> for the kernels the family does not specialise -- and launches it.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F>
+static inline int32_t task_launch(bool revolute, int lanes, F launch) {
+    if (revolute) { if (lanes == 64) launch(int_c<1>(), int_c<64>()); else launch(int_c<1>(), int_c<32>()); }
+    else { if (lanes == 64) launch(int_c<3>(), int_c<64>()); else launch(int_c<3>(), int_c<32>()); }
+    return launch_status();
+}
+
+// both reset launches: `n` lane groups per row of the grid
+template <bool RNG>
+static int32_t reset_launch(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
+                            const phc_im_buffers_t* buf, int n, const int64_t* env_ids, const float* phase, int start_at_zero, uint64_t key, void* stream) {
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto dpj, auto g) {
+        hipLaunchKernelGGL((k_im_reset<dpj(), RNG, g()>), dim3(env_blocks(n, g()), prm->num_amp_obs_steps + 2), dim3(256), 0, (hipStream_t)stream, *model, *lib,
+                           *prm, *sim, *buf, n, env_ids, phase, start_at_zero, key);
+    });
+}
+
 extern "C" {
 
 int32_t phc_abi_version(void) { return PHC_ABI_VERSION; }
@@ -289,15 +258,11 @@ int32_t phc_motion_state(const phc_motion_lib_t* lib, int32_t n, const int64_t* 
                          const float* offset, float* rg_pos, float* rb_rot, float* body_vel, float* body_ang_vel,
                          float* dof_pos, float* dof_vel, int64_t* frame_idx0, int64_t* frame_idx1, float* blend, float* rg_pos_ext,
                          float* rb_rot_ext, void* stream) {
-    if (!lib || n < 0 || lib->num_bodies + lib->num_ext_bodies > PHC_MAX_BODIES) return PHC_EINVAL;
-    if (n == 0) return 0;
-    if (group_lanes(lib->num_bodies, lib->num_ext_bodies) == 64)
-        hipLaunchKernelGGL(k_motion_state<64>, dim3(env_blocks(n, 64)), dim3(256), 0, (hipStream_t)stream, *lib, n, motion_ids, motion_times, offset,
+    if (int32_t rc = check_motion_state(lib, n); rc || n == 0) return rc;
+    return task_launch(lib->dofs_per_joint == 1, group_lanes(lib->num_bodies, lib->num_ext_bodies), [&](auto, auto g) {
+        hipLaunchKernelGGL(k_motion_state<g()>, dim3(env_blocks(n, g())), dim3(256), 0, (hipStream_t)stream, *lib, n, motion_ids, motion_times, offset,
                            rg_pos, rb_rot, body_vel, body_ang_vel, dof_pos, dof_vel, frame_idx0, frame_idx1, blend, rg_pos_ext, rb_rot_ext);
-    else
-        hipLaunchKernelGGL(k_motion_state<32>, dim3(env_blocks(n, 32)), dim3(256), 0, (hipStream_t)stream, *lib, n, motion_ids, motion_times, offset,
-                           rg_pos, rb_rot, body_vel, body_ang_vel, dof_pos, dof_vel, frame_idx0, frame_idx1, blend, rg_pos_ext, rb_rot_ext);
-    return launch_status();
+    });
 }
 
 int32_t phc_sample_time_interval(const phc_motion_lib_t* lib, int32_t n, const int64_t* motion_ids, const float* phase,
@@ -308,124 +273,59 @@ int32_t phc_sample_time_interval(const phc_motion_lib_t* lib, int32_t n, const i
     return launch_status();
 }
 
-static int32_t check_model(const phc_model_t* m) {
-    if (!m || m->num_bodies < 1 || m->num_bodies > PHC_MAX_BODIES || !m->ints || !m->floats) return PHC_EINVAL;
-    // all-spherical (SMPL family) or all-revolute (H1 / G1) articulations
-    if (m->num_dof != 3 * (m->num_bodies - 1) && m->num_dof != m->num_bodies - 1) return PHC_EUNSUPPORTED;
-    return 0;
-}
-
-static int32_t check_im(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm) {
-    int32_t rc = check_model(model);
-    if (rc) return rc;
-    if (!lib || !prm || lib->num_bodies != model->num_bodies) return PHC_EINVAL;
-    const int dpj = model->num_dof == model->num_bodies - 1 && model->num_bodies > 2 ? 1 : 3;
-    if ((lib->dofs_per_joint == 1 ? 1 : 3) != dpj || (prm->dofs_per_joint == 1 ? 1 : 3) != dpj) return PHC_EINVAL;
-    if (prm->num_ext_bodies < 0 || prm->num_ext_bodies != lib->num_ext_bodies || model->num_bodies + prm->num_ext_bodies > PHC_MAX_BODIES) return PHC_EINVAL;
-    if (prm->num_ext_bodies > 0 && (!prm->ext_parent || !prm->ext_offset)) return PHC_EINVAL;
-    if (!prm->track_slot || !prm->reset_mask || !prm->termination_distances || !prm->key_body_ids || !prm->amp_joint_slot) return PHC_EINVAL;
-    if (prm->num_key_bodies > 32) return PHC_EUNSUPPORTED;
-    return 0;
-}
-
 int32_t phc_im_post_physics(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm,
                             const phc_sim_state_t* sim, const phc_im_buffers_t* buf, void* stream) {
-    int32_t rc = check_im(model, lib, prm);
-    if (rc) return rc;
-    if (!sim || !buf || buf->amp_obs_in == buf->amp_obs_out) return PHC_EINVAL;
-    if (prm->cycle_motion && (!buf->cycle_counter || !buf->cycle_phase)) return PHC_EINVAL;
-    if (prm->zero_out_far && (!buf->point_goal || prm->track_slot == nullptr)) return PHC_EINVAL;
-    if (sim->num_envs == 0) return 0;
+    if (int32_t rc = check_im_post_physics(model, lib, prm, sim, buf); rc || sim->num_envs == 0) return rc;
     const int n_reset_bodies = prm->num_reset_bodies > 0 ? prm->num_reset_bodies : 1;
-    const int g = group_lanes(model->num_bodies, prm->num_ext_bodies);
-    const dim3 grid(env_blocks(sim->num_envs, g));
-#define PHC_POST(DPJ, G) hipLaunchKernelGGL((k_im_post_physics<DPJ, G>), grid, dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim, *buf, n_reset_bodies)
-    if (prm->dofs_per_joint == 1) { if (g == 64) PHC_POST(1, 64); else PHC_POST(1, 32); }
-    else { if (g == 64) PHC_POST(3, 64); else PHC_POST(3, 32); }
-#undef PHC_POST
-    return launch_status();
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto dpj, auto g) {
+        hipLaunchKernelGGL((k_im_post_physics<dpj(), g()>), dim3(env_blocks(sim->num_envs, g())), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim,
+                           *buf, n_reset_bodies);
+    });
 }
 
 int32_t phc_amp_ref_table(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, int64_t num_frames,
                           const int64_t* next_frame, float* table, void* stream) {
-    int32_t rc = check_im(model, lib, prm);
-    if (rc) return rc;
-    if (!table || !next_frame || num_frames < 0 || num_frames > lib->num_frames_total) return PHC_EINVAL;
-    if (num_frames == 0) return 0;
-    const int g = group_lanes(model->num_bodies, prm->num_ext_bodies);
-    const int64_t blocks = (num_frames * g + 255) / 256;
-    if (blocks > 0x7fffffffLL) return PHC_EUNSUPPORTED;
-#define PHC_TAB(DPJ, G) hipLaunchKernelGGL((k_amp_ref_table<DPJ, G>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, num_frames, next_frame, table)
-    if (prm->dofs_per_joint == 1) { if (g == 64) PHC_TAB(1, 64); else PHC_TAB(1, 32); }
-    else { if (g == 64) PHC_TAB(3, 64); else PHC_TAB(3, 32); }
-#undef PHC_TAB
-    return launch_status();
+    if (int32_t rc = check_amp_ref_table(model, lib, prm, num_frames, next_frame, table); rc || num_frames == 0) return rc;
+    const int lanes = group_lanes(model->num_bodies, prm->num_ext_bodies);
+    const int64_t blocks = (num_frames * lanes + 255) / 256;
+    if (blocks > 0x7fffffffLL) return PHC_EUNSUPPORTED;   // (launch geometry, not an argument check: grid.x is 31 bits)
+    return task_launch(prm->dofs_per_joint == 1, lanes, [&](auto dpj, auto g) {
+        hipLaunchKernelGGL((k_amp_ref_table<dpj(), g()>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, num_frames, next_frame,
+                           table);
+    });
 }
 
 int32_t phc_im_reset(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
                      const phc_im_buffers_t* buf, int32_t num_reset, const int64_t* env_ids, const float* phase,
                      int32_t start_at_zero, void* stream) {
-    int32_t rc = check_im(model, lib, prm);
-    if (rc) return rc;
-    if (!sim || !buf || num_reset < 0 || (!start_at_zero && !phase)) return PHC_EINVAL;
-    if (num_reset == 0) return 0;
-    const int g = group_lanes(model->num_bodies, prm->num_ext_bodies);
-    const dim3 grid(env_blocks(num_reset, g), prm->num_amp_obs_steps + 2);
-#define PHC_RESET(DPJ, G) hipLaunchKernelGGL((k_im_reset<DPJ, false, G>), grid, dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim, *buf, num_reset, env_ids, phase, start_at_zero, 0ull)
-    if (prm->dofs_per_joint == 1) { if (g == 64) PHC_RESET(1, 64); else PHC_RESET(1, 32); }
-    else { if (g == 64) PHC_RESET(3, 64); else PHC_RESET(3, 32); }
-#undef PHC_RESET
-    return launch_status();
+    if (int32_t rc = check_im_reset(model, lib, prm, sim, buf, num_reset, phase, start_at_zero); rc || num_reset == 0) return rc;
+    return reset_launch<false>(model, lib, prm, sim, buf, num_reset, env_ids, phase, start_at_zero, 0ull, stream);
 }
 
 int32_t phc_im_reset_done(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
                           const phc_im_buffers_t* buf, uint64_t seed, uint64_t counter, int32_t start_at_zero, void* stream) {
-    int32_t rc = check_im(model, lib, prm);
-    if (rc) return rc;
-    if (!sim || !buf) return PHC_EINVAL;
-    if (sim->num_envs == 0) return 0;
-    if (buf->reset_list && (!buf->reset_count || buf->reset_sublist_cap * PHC_RESET_SUBLISTS < sim->num_envs)) return PHC_EINVAL;
+    if (int32_t rc = check_im_reset_done(model, lib, prm, sim, buf); rc || sim->num_envs == 0) return rc;
     const int n = buf->reset_list ? buf->reset_sublist_cap * PHC_RESET_SUBLISTS : sim->num_envs;   // groups to launch
-    // (with a device-side call counter the host one stays out of the key: a captured launch and an eager one then draw the same numbers)
-    const uint64_t key = splitmix64(splitmix64(seed) ^ ((buf->reset_rng_counter ? 0ull : counter) * 0xD1342543DE82EF95ull));
-    const int g = group_lanes(model->num_bodies, prm->num_ext_bodies);
-    const dim3 grid(env_blocks(n, g), prm->num_amp_obs_steps + 2);
-#define PHC_RESET(DPJ, G) hipLaunchKernelGGL((k_im_reset<DPJ, true, G>), grid, dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim, *buf, n, nullptr, nullptr, start_at_zero, key)
-    if (prm->dofs_per_joint == 1) { if (g == 64) PHC_RESET(1, 64); else PHC_RESET(1, 32); }
-    else { if (g == 64) PHC_RESET(3, 64); else PHC_RESET(3, 32); }
-#undef PHC_RESET
-    return launch_status();
+    return reset_launch<true>(model, lib, prm, sim, buf, n, nullptr, nullptr, start_at_zero, im_reset_done_key(*buf, seed, counter), stream);
 }
 
 int32_t phc_im_reset_from_state(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm,
                                 const phc_sim_state_t* sim, const phc_im_buffers_t* buf, int32_t num_reset, const int64_t* env_ids,
                                 int32_t fill_history, void* stream) {
-    int32_t rc = check_im(model, lib, prm);
-    if (rc) return rc;
-    if (!sim || !buf || num_reset < 0 || (num_reset > 0 && !env_ids)) return PHC_EINVAL;
-    if (num_reset == 0) return 0;
-    if (group_lanes(model->num_bodies, prm->num_ext_bodies) == 64)
-        hipLaunchKernelGGL(k_im_reset_from_state<64>, dim3(env_blocks(num_reset, 64)), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim,
-                           *buf, num_reset, env_ids, fill_history);
-    else
-        hipLaunchKernelGGL(k_im_reset_from_state<32>, dim3(env_blocks(num_reset, 32)), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim,
-                           *buf, num_reset, env_ids, fill_history);
-    return launch_status();
+    if (int32_t rc = check_im_reset_from_state(model, lib, prm, sim, buf, num_reset, env_ids); rc || num_reset == 0) return rc;
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto, auto g) {
+        hipLaunchKernelGGL(k_im_reset_from_state<g()>, dim3(env_blocks(num_reset, g())), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim, *buf,
+                           num_reset, env_ids, fill_history);
+    });
 }
 
 int32_t phc_amp_obs_demo(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, int32_t n,
                          const int64_t* motion_ids, const float* motion_times0, float* amp_obs_demo, void* stream) {
-    int32_t rc = check_im(model, lib, prm);
-    if (rc) return rc;
-    if (n < 0) return PHC_EINVAL;
-    if (n == 0) return 0;
-    if (group_lanes(model->num_bodies, prm->num_ext_bodies) == 64)
-        hipLaunchKernelGGL(k_amp_obs_demo<64>, dim3(env_blocks(n, 64), prm->num_amp_obs_steps), dim3(256), 0, (hipStream_t)stream, *model, *lib,
-                           *prm, n, motion_ids, motion_times0, amp_obs_demo);
-    else
-        hipLaunchKernelGGL(k_amp_obs_demo<32>, dim3(env_blocks(n, 32), prm->num_amp_obs_steps), dim3(256), 0, (hipStream_t)stream, *model, *lib,
-                           *prm, n, motion_ids, motion_times0, amp_obs_demo);
-    return launch_status();
+    if (int32_t rc = check_amp_obs_demo(model, lib, prm, n); rc || n == 0) return rc;
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto, auto g) {
+        hipLaunchKernelGGL(k_amp_obs_demo<g()>, dim3(env_blocks(n, g()), prm->num_amp_obs_steps), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, n,
+                           motion_ids, motion_times0, amp_obs_demo);
+    });
 }
 
 int32_t phc_gae(int32_t horizon, int32_t n, const float* fdones, const float* values, const float* rewards,

@@ -228,6 +228,43 @@ PHC_HD void st_joint(float* p, int dpj, V3 v) {
     if (dpj != 1) { p[1] = v.y; p[2] = v.z; }
 }
 
+// M9 standalone (phc_motion_state): lookup i of a list of (id, time) pairs, the part of lane `lane` -- body `lane`, or extended body `lane - NB`.
+// Every output array is optional.
+PHC_HD void motion_state_lane(const phc_motion_lib_t& lib, int64_t i, int lane, const int64_t* ids, const float* times, const float* offset, float* rg_pos, float* rb_rot,
+                              float* body_vel, float* body_ang_vel, float* dof_pos, float* dof_vel, int64_t* idx0, int64_t* idx1, float* blend, float* rg_pos_ext, float* rb_rot_ext) {
+    const int nb = lib.num_bodies;
+    const FrameRef fr = frame_ref(lib, ids[i], times[i]);
+    if (lane == 0) {
+        if (idx0) idx0[i] = fr.idx0;
+        if (idx1) idx1[i] = fr.idx1;
+        if (blend) blend[i] = fr.blend;
+    }
+    if (lane >= nb) {
+        const int e = lane - nb, ne = lib.num_ext_bodies;
+        if (e < ne && (rg_pos_ext || rb_rot_ext)) {
+            V3 p; Q4 q;
+            ref_body_ext(lib, fr, e, &p, &q);
+            if (offset) p += ld3(offset + i * 3);
+            if (rg_pos_ext) st3(rg_pos_ext + (i * ne + e) * 3, p);
+            if (rb_rot_ext) st4(rb_rot_ext + (i * ne + e) * 4, q);
+        }
+        return;
+    }
+    BodyState s = ref_body(lib, fr, lane);
+    if (offset) s.pos += ld3(offset + i * 3);
+    if (rg_pos) st3(rg_pos + (i * nb + lane) * 3, s.pos);
+    if (rb_rot) st4(rb_rot + (i * nb + lane) * 4, s.rot);
+    if (body_vel) st3(body_vel + (i * nb + lane) * 3, s.vel);
+    if (body_ang_vel) st3(body_ang_vel + (i * nb + lane) * 3, s.angvel);
+    if (lane >= 1 && (dof_pos || dof_vel)) {
+        V3 dp, dv;
+        ref_joint(lib, fr, lane, &dp, &dv);
+        const int dpj = lib.dofs_per_joint == 1 ? 1 : 3;
+        if (dof_pos) st_joint(dof_pos + (i * (nb - 1) + (lane - 1)) * dpj, dpj, dp);
+        if (dof_vel) st_joint(dof_vel + (i * (nb - 1) + (lane - 1)) * dpj, dpj, dv);
+    }
+}
+
 PHC_HD BodyState load_body(const float* rigid_body_state, int64_t env, int nb, int j) {
     const float* p = rigid_body_state + (env * nb + j) * 13;
     BodyState s;

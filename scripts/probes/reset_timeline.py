@@ -1,4 +1,4 @@
-"""One lane group's timeline through k_im_reset (instrumented library; s_memtime + s_waitcnt(0) at five points).
+"""One lane group's timeline through k_im_reset (instrumented library; s_memtime + s_waitcnt(0) at four points).
     python scripts/probes/reset_timeline.py [num_envs]"""
 import ctypes as C
 import os
@@ -25,14 +25,14 @@ def main():
         task.reset_done(); env.step(a)
     torch.cuda.synchronize()
     print(f"{n} envs, {int((task.reset_buf != 0).sum())} envs reset this step")
-    names = ["list entry -> env", "motion id -> start time", "state + self obs (y = 0) / task obs (y = 1)", "AMP history frame (y >= 2)"]
+    names = ["the reset pick: list entry -> env -> start time", "state + self obs (y = 0) / task obs (y = 1)", "AMP history frame (y >= 2)"]
     for r, k in ((3, 0), (200, 0), (3, 1), (200, 1), (3, 2), (3, 7), (200, 11)):
         buf = (C.c_ulonglong * 64)()
         raw.phc_debug_reset_timeline(buf, r * 16 + k)
         task.reset_done(); env.step(a)
         torch.cuda.synchronize()
         raw.phc_debug_reset_timeline(buf, -1)
-        t = [int(buf[i]) for i in range(5)]
+        t = [int(buf[i]) for i in (0, 2, 3, 4)]   # (stamp 1 stood inside what is now the reset pick of phc_im.h)
         if not all(t):
             print(f"group r={r} y={k}: not an active group this step {t}")
             continue

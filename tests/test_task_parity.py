@@ -3,6 +3,9 @@
   * the numpy oracle for compositions the reference cannot run without Isaac Gym.
 Each test runs on two backends (tests/backends.py): `hostemu` = the kernels' per-lane functions compiled
 with g++ (CPU, test infrastructure) and `hip` = the real kernels through the C ABI on an MI355X (-m gpu)."""
+import copy
+import types
+
 import numpy as np
 import pytest
 
@@ -865,3 +868,226 @@ def test_multi_step_rollout_vs_reference_env(golden, backend):
         np.testing.assert_allclose(be.np(amp[cur]), g["amp"][k], atol=2e-5, err_msg=f"step {k}: AMP history")
         n_term += int(g["terminate"][k].sum())
     assert n_resets >= N + 8 and n_term >= 5      # the sequence really exercises resets after time-outs and after terminations
+
+
+# ---- what the seven task entry points refuse (phc_amd/csrc/phc_im_check.h), on both backends ----------------------------------------------------------------
+EINVAL, EUNSUPPORTED = -1, -2      # PHC_EINVAL / PHC_EUNSUPPORTED
+MAX_BODIES = 64                    # PHC_MAX_BODIES
+
+
+def _refusal_args(be, gl, model, mstruct, lib):
+    """One valid argument set for all seven entry points (the buffers of test_amp_demo_and_reset_vs_oracle) and every array a launch could write, with the
+    sentinel content it was given."""
+    N, nb, nd, S, A = 6, 24, 69, 10, 196
+    prm, _ = make_im_params(be, model, N)
+    out = dict(root=(N, 13), dof=(N, nd, 2), rbs=(N, nb, 13), cf=(N, nb, 3), df=(N, nd), pd=(N, nd), rew=(N,), raw=(N, 5), obs=(N, 934), amp_in=(N, S, A),
+               amp_out=(N, S, A), st=(N,), so=(N,), goff=(N, 3), demo=(4, S, A), ms_pos=(4, nb, 3), ms_rot=(4, nb, 4), ms_vel=(4, nb, 3), ms_ang=(4, nb, 3),
+               ms_dp=(4, nd), ms_dv=(4, nd), ms_blend=(4,), point_goal=(N,), cycle_phase=(N,))
+    first = {k: np.full(shp, 7, F) for k, shp in out.items()}
+    first.update(progress=np.full(N, 7, np.int64), reset=np.ones(N, np.int64), term=np.full(N, 7, np.int64), ms_i0=np.full(4, 7, np.int64),
+                 ms_i1=np.full(4, 7, np.int64), cycle_counter=np.full(N, 7, np.int32))
+    cap = abi.reset_sublist_cap(N)
+    first.update(rl=np.full(abi.RESET_SUBLISTS * cap, 7, np.int32), rc=np.zeros((3, abi.RESET_SUBLISTS, abi.RESET_COUNT_STRIDE), np.int32))   # (empty lists)
+    nf, starts = gl["motion_num_frames"].astype(np.int64), gl["length_starts"].astype(np.int64)
+    Ftot = int(starts[-1] + nf[-1])
+    first["table"] = np.full((Ftot, A), 7, F)
+    d = {k: be.arr(v) for k, v in first.items()}
+    nxt = np.arange(1, Ftot + 1, dtype=np.int64)
+    nxt[starts + nf - 1] = starts + nf - 1
+    a = types.SimpleNamespace(model=mstruct, lib=lib, prm=prm, n=4, saz=0, nframes=Ftot, nxt=be.arr(nxt), table=d["table"], demo=d["demo"],
+                              mids=be.arr(np.arange(N, dtype=np.int64)), env_ids=be.arr(np.array([4, 1, 2, 0], np.int64)), phase=be.arr(np.full(4, 0.5, F)),
+                              ids=be.arr(np.array([0, 1, 2, 3], np.int64)), t0=be.arr(np.full(4, 0.5, F)),
+                              ms=[d[k] for k in ("ms_pos", "ms_rot", "ms_vel", "ms_ang", "ms_dp", "ms_dv", "ms_i0", "ms_i1", "ms_blend")])
+    a.sim = abi.sim_state_struct(N, d["root"], d["dof"], d["rbs"], d["cf"], d["df"], d["pd"])
+    a.buf = abi.im_buffers_struct(d["progress"], d["reset"], d["term"], d["rew"], d["raw"], d["obs"], d["amp_in"], d["amp_out"], a.mids, d["st"], d["so"],
+                                  d["goff"], reset_list=d["rl"], reset_count=d["rc"], reset_slot=1)
+    return a, d, first
+
+
+def _with(a, name, **fields):
+    """`a` with a copy of its struct `name` (None: a null pointer) whose `fields` are changed."""
+    a = copy.copy(a)
+    if fields:
+        s = type(getattr(a, name)).from_buffer_copy(getattr(a, name))
+        for k, v in fields.items():
+            setattr(s, k, abi.ptr(v) if hasattr(v, "shape") else v)
+        setattr(a, name, s)
+    else:
+        setattr(a, name, None)
+    return a
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_task_entry_points_refuse_before_they_launch(golden, backend):
+    """Every condition of phc_im_check.h, one at a time from a valid argument set, through each entry point it belongs to: the stated code comes back and no
+    array a launch could write has changed -- the refusal stands in front of the launch (hip) and of the loop (host emulation) alike.  No case passes the
+    check with arguments a launch could not run on."""
+    be = get_backend(backend)
+    gl = golden("motion_lib_eval")
+    model, mstruct, keepm = model_on(be)
+    lib, keep = motion_lib_on(be, gl)
+    calls = dict(
+        motion_state=lambda a: be.motion_state(a.lib, a.n, a.ids, a.t0, None, *a.ms),
+        table=lambda a: be.amp_ref_table(a.model, a.lib, a.prm, a.nframes, a.nxt, a.table),
+        demo=lambda a: be.amp_obs_demo(a.model, a.lib, a.prm, a.n, a.ids, a.t0, a.demo),
+        reset=lambda a: be.im_reset(a.model, a.lib, a.prm, a.sim, a.buf, a.n, a.env_ids, a.phase, a.saz),
+        post=lambda a: be.im_post_physics(a.model, a.lib, a.prm, a.sim, a.buf),
+        reset_done=lambda a: be.im_reset_done(a.model, a.lib, a.prm, a.sim, a.buf, 3, 1, a.saz),
+        from_state=lambda a: be.im_reset_from_state(a.model, a.lib, a.prm, a.sim, a.buf, a.n, a.env_ids, 1))
+    ok, ok_dev, _ = _refusal_args(be, gl, model, mstruct, lib)      # (`ok_dev`: the structs hold raw addresses of these arrays)
+    for name, call in calls.items():      # the valid set (the reset imposes a state before post-physics reads one)
+        assert call(ok) == 0, name
+    be.sync()
+    a, dev, first = _refusal_args(be, gl, model, mstruct, lib)
+    im = [k for k in calls if k != "motion_state"]      # the entry points behind check_im
+    some = a.phase                                    # any valid address
+    cases = [
+        # check_model (phc_sim_check.h): the same for the task launches and the stepper
+        (im, _with(a, "model"), EINVAL), (im, _with(a, "model", num_bodies=0), EINVAL), (im, _with(a, "model", num_bodies=MAX_BODIES + 1), EINVAL),
+        (im, _with(a, "model", ints=None), EINVAL), (im, _with(a, "model", floats=None), EINVAL), (im, _with(a, "model", num_dof=5), EUNSUPPORTED),
+        (im, _with(a, "model", num_dof=23, num_shapes=2, int_stride=8, float_stride=8), EUNSUPPORTED),     # per-env shapes on a revolute model
+        (im, _with(a, "model", num_shapes=2, int_stride=0, float_stride=8), EINVAL), (im, _with(a, "model", num_shapes=2, int_stride=8, float_stride=-1), EINVAL),
+        # check_im
+        (im, _with(a, "lib"), EINVAL), (im, _with(a, "prm"), EINVAL), (im, _with(a, "lib", num_bodies=23), EINVAL),
+        (im, _with(a, "lib", dofs_per_joint=1), EINVAL), (im, _with(a, "prm", dofs_per_joint=1), EINVAL), (im, _with(a, "model", num_dof=23), EINVAL),
+        (im, _with(a, "prm", num_ext_bodies=-1), EINVAL), (im, _with(a, "prm", num_ext_bodies=1), EINVAL),
+        (im, _with(_with(a, "lib", num_ext_bodies=41), "prm", num_ext_bodies=41, ext_parent=some, ext_offset=some), EINVAL),
+        (im, _with(_with(a, "lib", num_ext_bodies=2), "prm", num_ext_bodies=2), EINVAL),
+        (im, _with(_with(a, "lib", num_ext_bodies=2), "prm", num_ext_bodies=2, ext_parent=some), EINVAL),
+        (im, _with(_with(a, "lib", num_ext_bodies=2), "prm", num_ext_bodies=2, ext_offset=some), EINVAL),
+        *[(im, _with(a, "prm", **{t: None}), EINVAL) for t in ("track_slot", "reset_mask", "termination_distances", "key_body_ids", "amp_joint_slot")],
+        (im, _with(a, "prm", num_key_bodies=33), EUNSUPPORTED),
+        # the entry points' own conditions
+        (["post", "reset", "reset_done", "from_state"], _with(a, "sim"), EINVAL), (["post", "reset", "reset_done", "from_state"], _with(a, "buf"), EINVAL),
+        (["post"], _with(a, "buf", amp_obs_out=dev["amp_in"]), EINVAL),
+        (["post"], _with(a, "prm", cycle_motion=1), EINVAL), (["post"], _with(_with(a, "prm", cycle_motion=1), "buf", cycle_counter=dev["cycle_counter"]), EINVAL),
+        (["post"], _with(_with(a, "prm", cycle_motion=1), "buf", cycle_phase=dev["cycle_phase"]), EINVAL),
+        (["post"], _with(a, "prm", zero_out_far=1), EINVAL),
+        (["reset", "from_state", "demo", "motion_state"], types.SimpleNamespace(**{**vars(a), "n": -1}), EINVAL),
+        (["reset"], types.SimpleNamespace(**{**vars(a), "phase": None}), EINVAL),
+        (["from_state"], types.SimpleNamespace(**{**vars(a), "env_ids": None}), EINVAL),
+        (["reset_done"], _with(a, "buf", reset_count=None), EINVAL), (["reset_done"], _with(a, "buf", reset_sublist_cap=0), EINVAL),
+        (["reset_done"], _with(_with(a, "sim", num_envs=300), "buf", reset_sublist_cap=18), EINVAL),      # 18 * 16 < 300
+        (["table"], types.SimpleNamespace(**{**vars(a), "table": None}), EINVAL), (["table"], types.SimpleNamespace(**{**vars(a), "nxt": None}), EINVAL),
+        (["table"], types.SimpleNamespace(**{**vars(a), "nframes": -1}), EINVAL), (["table"], types.SimpleNamespace(**{**vars(a), "nframes": a.nframes + 1}), EINVAL),
+        (["motion_state"], _with(a, "lib"), EINVAL), (["motion_state"], _with(a, "lib", num_ext_bodies=41), EINVAL),
+    ]
+    for i, (names, bad, code) in enumerate(cases):
+        for name in names:
+            assert calls[name](bad) == code, (i, name)
+    # "nothing to do" is accepted in front of the conditions behind it, as before: no envs, and a reset list without counters
+    assert calls["reset_done"](_with(_with(a, "sim", num_envs=0), "buf", reset_count=None)) == 0
+    be.sync()
+    for k, v in dev.items():
+        np.testing.assert_array_equal(be.np(v), first[k], err_msg=k)
+
+
+# ---- phc_im_reset_done on the device-built list of finished envs ---------------------------------------------------------------------------------------------
+def _mix64(z):
+    """splitmix64 (phc_rng.h)"""
+    m = (1 << 64) - 1
+    z = (z + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def _hash_u01(key, env):
+    """hash_u01 (phc_rng.h): integer arithmetic, then an exact conversion of 24 bits"""
+    m = (1 << 32) - 1
+    x = ((env * 0x9E3779B1) & m) ^ (key & m)
+    x ^= x >> 16; x = (x * 0x85EBCA6B) & m; x ^= x >> 13; x = (x * 0xC2B2AE35) & m; x ^= x >> 16
+    x = (x + (key >> 32)) & m
+    x ^= x >> 15; x = (x * 0x2C1B3C6D) & m; x ^= x >> 12; x = (x * 0x297A2D39) & m; x ^= x >> 15
+    return F(x >> 8) * F(1.0 / 16777216.0)
+
+
+def _reset_done_case(be, golden, rb, N):
+    """-> model struct, library, parameters, (NB, ND, observation width, AMP width), clip lengths, keep-alive"""
+    if rb == "smpl":
+        gl = golden("motion_lib_eval")
+        model, mstruct, keepm = model_on(be)
+        lib, keep = motion_lib_on(be, gl)
+        prm, keepp = make_im_params(be, model, N)
+        return mstruct, lib, prm, (24, 69, 934, 196), gl["motion_lengths"], (keepm, keep, keepp)
+    from test_h1 import _lib_from_golden, robot_im_params      # the robot model and library of tests/test_h1.py: one DoF per joint, extended bodies
+    g = golden(f"task_fns_{rb}")
+    gl = _lib_from_golden(golden, rb)
+    model, mstruct, keepm = model_on(be, f"{rb}_humanoid")
+    lib, keep = motion_lib_on(be, gl)
+    prm = robot_im_params(be, model, g["ext_parent"], g["ext_pos"], rb)
+    NB = model.num_bodies
+    return mstruct, lib, prm, (NB, NB - 1, NB * 15 - 2 + NB * 24, 13 + 2 * (NB - 1) + 12), gl["motion_lengths"], (keepm, keep)
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("rb", ["smpl", "h1", "g1"])      # (3 DoFs per joint, 32 lanes) / (1, 32, extended bodies) / (1, 64: 38 bodies)
+def test_reset_done_on_the_device_list_equals_the_masked_sweep(golden, backend, rb):
+    """phc_im_reset_done works either on the lists of finished envs that the post-physics launch builds on the device (16 sub-lists, sub-list (env / 8) % 16,
+    counted in slot `reset_slot`) or, without lists, sweeps all envs for a set reset flag.  Lists written by hand the way im_post_finalize fills them: both
+    modes leave every buffer bit-identical, with the draws keyed by the device-side call counter and by the host's; envs whose flag is clear keep every
+    value; the list launch zeroes the NEXT slot's counters and no other; the start times are the counter-keyed draws of phc_rng.h, restated in integers
+    here; and from time zero the result is phc_im_reset's over the same envs."""
+    be = get_backend(backend)
+    N, S = 300, 10                                   # 38 blocks of 8 envs: sub-lists of 2 or 3 blocks
+    mstruct, lib, prm, (nb, nd, n_obs, A), lengths, keepalive = _reset_done_case(be, golden, rb, N)
+    cap = abi.reset_sublist_cap(N)
+    assert cap == 24
+    rng = np.random.default_rng(11)
+    mids = rng.integers(0, len(lengths), N).astype(np.int64)
+    flagged = np.array(list(range(8)) + [13, 17, 18, 130, 255, 296, 298, 299])      # a whole block, two blocks in sub-list 0, a partial last block, the last env
+    flags = np.zeros(N, np.int64)
+    flags[flagged] = 1
+    clear = np.nonzero(flags == 0)[0]
+    slot = 1
+    rl = np.full((abi.RESET_SUBLISTS, cap), 100, np.int32)      # (entries behind a count are never read; 100 is an env whose flag is clear)
+    rc = np.zeros((3, abi.RESET_SUBLISTS, abi.RESET_COUNT_STRIDE), np.int32)
+    rc[0, :, 0], rc[2, :, 0] = 5, 9
+    for env in flagged:
+        sub = (env >> 3) & (abi.RESET_SUBLISTS - 1)
+        rl[sub, rc[slot, sub, 0]] = env
+        rc[slot, sub, 0] += 1
+    assert (rc[slot, :, 0] == 0).sum() >= 8 and rc[slot, 0, 0] == 9      # empty sub-lists, and one fed by two blocks
+    first = dict(root=np.full((N, 13), 0.5, F), dof=np.full((N, nd, 2), 0.5, F), rbs=np.full((N, nb, 13), 0.5, F), cf=np.ones((N, nb, 3), F),
+                 df=np.ones((N, nd), F), pd=np.full((N, nd), 0.5, F), progress=np.full(N, 7, np.int64), reset=flags, term=np.ones(N, np.int64),
+                 obs=np.full((N, n_obs), 0.25, F), amp=np.full((N, S, A), 0.25, F), st=np.full(N, -1, F), so=np.full(N, 3, F), goff=np.ones((N, 3), F),
+                 rbp=np.full((N, nb, 3), 0.25, F), rbr=np.full((N, nb, 4), 0.25, F), rbv=np.full((N, nb, 3), 0.25, F), rdp=np.full((N, nd), 0.25, F),
+                 rl=rl.reshape(-1), rc=rc, rngc=np.array([5], np.int64))
+    mids_d, keep_dev = be.arr(mids), []
+
+    def run(listed, device_counter, counter, start_at_zero, env_ids=None):
+        d = {k: be.arr(v) for k, v in first.items()}
+        keep_dev.append(d)      # (the structs hold raw addresses)
+        sim = abi.sim_state_struct(N, d["root"], d["dof"], d["rbs"], d["cf"], d["df"], d["pd"])
+        buf = abi.im_buffers_struct(d["progress"], d["reset"], d["term"], be.zeros(N), be.zeros((N, 5)), d["obs"], d["amp"], d["amp"], mids_d, d["st"], d["so"],
+                                    d["goff"], ref_body_pos=d["rbp"], ref_body_rot=d["rbr"], ref_body_vel=d["rbv"], ref_dof_pos=d["rdp"],
+                                    reset_list=d["rl"] if listed else None, reset_count=d["rc"] if listed else None, reset_slot=slot,
+                                    reset_rng_counter=d["rngc"] if device_counter else None)
+        if env_ids is None:
+            assert be.im_reset_done(mstruct, lib, prm, sim, buf, 1234, counter, start_at_zero) == 0
+        else:
+            assert be.im_reset(mstruct, lib, prm, sim, buf, len(env_ids), be.arr(env_ids), None, start_at_zero) == 0
+        be.sync()
+        return {k: be.np(v) for k, v in d.items()}
+
+    per_env = [k for k in first if k not in ("rl", "rc", "rngc")]
+    for device_counter in (True, False):
+        lst, swp = run(True, device_counter, 42, 0), run(False, device_counter, 42, 0)
+        for k in per_env:
+            assert lst[k].tobytes() == swp[k].tobytes(), (device_counter, k)
+            np.testing.assert_array_equal(lst[k][clear], first[k][clear], err_msg=k)      # (the reset flags too: reset_done leaves them to the next step)
+        assert (lst["progress"][flagged] == 0).all() and (lst["term"][flagged] == 0).all() and (lst["cf"][flagged] == 0).all()
+        assert (lst["rc"][(slot + 1) % 3, :, 0] == 0).all()
+        np.testing.assert_array_equal(lst["rc"][[slot, (slot + 2) % 3]], rc[[slot, (slot + 2) % 3]])
+        np.testing.assert_array_equal(lst["rl"], first["rl"])
+        np.testing.assert_array_equal(swp["rc"], rc)
+        # with a device-side call counter the host's stays out of the key (phc_im_reset_done)
+        key = _mix64(_mix64(_mix64(1234)) ^ ((5 * 0x9E6C63D0876A9A47) & ((1 << 64) - 1))) if device_counter else _mix64(_mix64(1234) ^ ((42 * 0xD1342543DE82EF95) & ((1 << 64) - 1)))
+        u = np.array([_hash_u01(key, int(e)) for e in flagged], F)
+        np.testing.assert_array_equal(lst["st"][flagged], po.sample_time_interval(u, lengths[mids[flagged]]))
+        assert len(np.unique(lst["st"][flagged])) > 8
+    zero, ref = run(True, True, 42, 1), run(False, True, 42, 1, env_ids=flagged.astype(np.int64))
+    for k in per_env:
+        if k != "reset":
+            np.testing.assert_array_equal(zero[k], ref[k], err_msg=k)
+    assert (zero["st"][flagged] == 0).all() and (zero["reset"] == flags).all() and (ref["reset"] == 0).all()
