@@ -18,7 +18,6 @@ There is no CPU fallback: constructing the task without a HIP device raises.
 from collections import OrderedDict
 from enum import Enum
 import itertools
-
 import os
 
 import numpy as np
@@ -30,7 +29,7 @@ from ...model import load_model, pack_shapes
 from ...motion_lib import FixHeightMode, MotionLibReal, MotionLibSMPL
 from ... import robots
 from ...utils.flags import flags
-from ...utils.synthetic_motion import make_motion_dict, make_robot_motion_dict
+from ...utils.synthetic_motion import BASE_ROT, motion_from_spec
 
 _GENERATION = itertools.count(1)   # serial numbers behind HumanoidIm.launch_generation()
 
@@ -67,24 +66,52 @@ class HumanoidIm:
         Random = 2
         Hybrid = 3
 
+    # device-built list of the envs that finished in the last step (phc_im_buffers_t.reset_list): reset_done() works on it
+    _use_reset_list = True
+
     # ------------------------------------------------------------------ construction
     def __init__(self, cfg, sim_params=None, physics_engine=None, device_type="cuda", device_id=0, headless=True):
-        self.cfg = cfg
-        self.sim_params = sim_params
-        self.physics_engine = physics_engine
-        self.headless = headless
-        self.device_type, self.device_id = device_type, device_id
+        """The reference's class chain as phases, in its order.  The host phases (`_host_phases`: options, models, sizes, index tables,
+        phc_sim_params_t and every refusal) touch no device; the device phases behind them allocate and upload what those computed."""
+        self._set_args(cfg, sim_params, physics_engine, device_type, device_id, headless)
         if device_type not in ("cuda", "GPU"):
             raise RuntimeError("phc_amd.HumanoidIm runs on the HIP device only (device_type='cuda'); there is no CPU path")
         if not torch.cuda.is_available():
             raise RuntimeError("no HIP device visible: phc_amd has no CPU fallback")
-        self.device = f"cuda:{device_id}"
         self._lib = L.load()  # fails loudly if libphc_amd.so is missing
         torch.cuda.set_device(device_id)
-        env = cfg["env"]
-        robot = cfg["robot"]
+        self._host_phases()
+        self._upload_model()
+        self._upload_character_props()
+        self._allocate_buffers()
+        self._setup_action_scaling()
+        self._allocate_im_state()
+        self._load_motion(cfg["env"]["motion_file"])   # reference motions (humanoid_im.py:316-367)
 
-        # ---- load_humanoid_configs (humanoid.py:250-420) ----
+    @classmethod
+    def host_only(cls, cfg):
+        """The task as far as it is built without a device: the host phases alone, subclass overrides included.  For reading sizes, index tables,
+        phc_sim_params_t and refusals on a CPU; it cannot step (a launch-facing method fails on the first attribute a device phase makes)."""
+        self = cls.__new__(cls)
+        self._set_args(cfg, None, None, "cuda", 0, True)
+        self._host_phases()
+        return self
+
+    def _set_args(self, cfg, sim_params, physics_engine, device_type, device_id, headless):
+        self.cfg, self.sim_params, self.physics_engine, self.headless = cfg, sim_params, physics_engine, headless
+        self.device_type, self.device_id, self.device = device_type, device_id, f"cuda:{device_id}"
+
+    def _host_phases(self):
+        self._up = {}   # what the host phases computed for the device phases to upload (numpy arrays, lists)
+        self._load_humanoid_configs()
+        self._load_models()
+        self._setup_character_props()
+        self._setup_sim_params()
+        self._setup_im_options()
+
+    # ---- host phase: load_humanoid_configs (humanoid.py:250-420) ----
+    def _load_humanoid_configs(self):
+        cfg, env, robot = self.cfg, self.cfg["env"], self.cfg["robot"]
         self.humanoid_type = robot.get("humanoid_type", "smpl")
         if self.humanoid_type not in ("smpl", "h1", "g1"):
             raise NotImplementedError(f"humanoid_type={self.humanoid_type!r}: built so far: smpl, h1, g1")
@@ -132,18 +159,12 @@ class HumanoidIm:
             raise NotImplementedError("self_obs_v=2: SMPL family, without shape / limb-weight columns (the reference raises for them, humanoid.py:2101-2105)")
         # S6: force sensors at the feet (humanoid.py:268,1031-1040), read by self_obs_v 3 only (:683,1449,1481)
         self.force_sensor_joints = list(env.get("force_sensor_joints", ["L_Ankle", "R_Ankle"]))
-        if self._is_robot:  # load_robot_configs, humanoid.py:422-439
-            self._body_names_orig = list(robot["body_names"])
-            self._body_names = self._body_names_orig
-            self._dof_names = list(robot["dof_names"])
-            self._full_track_bodies = self._body_names_orig.copy()
-            self._eval_bodies = self._body_names_orig.copy()
-        else:
-            self._body_names_orig = list(SMPL_MUJOCO_NAMES)
-            self._body_names = self._body_names_orig
-            self._dof_names = self._body_names[1:]
-            self._full_track_bodies = self._body_names_orig.copy()
-            self._eval_bodies = [b for b in self._body_names_orig if b not in ("L_Toe", "R_Toe", "L_Hand", "R_Hand")]
+        # (robots: load_robot_configs, humanoid.py:422-439)
+        self._body_names_orig = list(robot["body_names"]) if self._is_robot else list(SMPL_MUJOCO_NAMES)
+        self._body_names = self._body_names_orig
+        self._dof_names = list(robot["dof_names"]) if self._is_robot else self._body_names[1:]
+        self._full_track_bodies = self._body_names_orig.copy()
+        self._eval_bodies = [b for b in self._body_names_orig if self._is_robot or b not in ("L_Toe", "R_Toe", "L_Hand", "R_Hand")]
         self._has_upright_start = robot.get("has_upright_start", True)   # False: observations strip the asset's base rotation (humanoid.py:1936-1939)
         self._has_shape_obs = robot.get("has_shape_obs", False)
         self._has_shape_obs_disc = robot.get("has_shape_obs_disc", False)
@@ -159,36 +180,22 @@ class HumanoidIm:
         self._freeze_hand = robot.get("freeze_hand", True)
         self._bias_offset = robot.get("bias_offset", False)
         self._has_smpl_pd_offset = robot.get("has_smpl_pd_offset", False)
-        self.shape_resampling_interval = env.get("shape_resampling_interval", 100)
-        self.getup_schedule = env.get("getup_schedule", False)
+        # options kept under their own name (load_common_humanoid_configs, humanoid.py:250-345)
+        for k, default in dict(shape_resampling_interval=100, getup_schedule=False, hard_negative=False, power_reward=False, power_coefficient=0.0005, kin_lr=5e-4,
+                               fitting=False, close_distance=0.25, far_distance=3, max_len=-1, eval_full=False, auto_pmcp=False, auto_pmcp_soft=False,
+                               strict_eval=False, add_obs_noise=False, start_idx=0, seq_motions=False, temp_running_mean=True, partial_running_mean=False).items():
+            setattr(self, k, env.get(k, default))
         self._kp_scale = env.get("kp_scale", 1.0)
         self._kd_scale = env.get("kd_scale", self._kp_scale)
-        self.hard_negative = env.get("hard_negative", False)
         self.cycle_motion = env.get("cycle_motion", False)       # humanoid.py:316
         self.cycle_motion_xp = env.get("cycle_motion_xp", False)  # humanoid.py:317 (a clip restart shifts the reference by up to a metre)
-        self.power_reward = env.get("power_reward", False)
-        self.power_coefficient = env.get("power_coefficient", 0.0005)
-        self.kin_lr = env.get("kin_lr", 5e-4)
-        self.fitting = env.get("fitting", False)
         self.z_readout = self.z_read = self.z_uniform = self.z_model = self.distill = self.kin_loss = False
         self.zero_out_far = env.get("zero_out_far", False)       # humanoid.py:325-330
         self.zero_out_far_train = env.get("zero_out_far_train", True)   # humanoid.py:315 (effective with zero_out_far only; the yamls set False)
-        self.close_distance = env.get("close_distance", 0.25)
-        self.far_distance = env.get("far_distance", 3)
         self._zero_out_far_steps = env.get("zero_out_far_steps", 90)
-        self.max_len = env.get("max_len", -1)
         self.models_path = env.get("models", [])
-        self.eval_full = env.get("eval_full", False)
-        self.auto_pmcp = env.get("auto_pmcp", False)
-        self.auto_pmcp_soft = env.get("auto_pmcp_soft", False)
-        self.strict_eval = env.get("strict_eval", False)
-        self.add_obs_noise = env.get("add_obs_noise", False)
         self._add_amp_input_noise = bool(env.get("add_amp_input_noise", False))   # humanoid_amp.py:135
-        self.start_idx = env.get("start_idx", 0)
-        self.seq_motions = env.get("seq_motions", False)
         self.collect_dataset = cfg.get("collect_dataset", False)
-        self.temp_running_mean = env.get("temp_running_mean", True)
-        self.partial_running_mean = env.get("partial_running_mean", False)
         self._full_body_reward = env.get("full_body_reward", True)   # False: reward over the tracked bodies only (humanoid_im.py:925-936)
         self._min_motion_len = env.get("min_length", -1)
         self.reward_specs = dict(env.get("reward_specs", {"k_pos": 100, "k_rot": 10, "k_vel": 0.1, "k_ang_vel": 0.1,
@@ -217,7 +224,9 @@ class HumanoidIm:
         self._num_amp_obs_enc_steps = env.get("numAMPEncObsSteps", self._num_amp_obs_steps)
         self.num_envs = env["num_envs"]
 
-        # ---- model (replaces create_sim / load_asset, humanoid.py:528-535,768-990) ----
+    # ---- host phase: model (replaces create_sim / load_asset, humanoid.py:528-535,768-990) ----
+    def _load_models(self):
+        cfg, env, robot = self.cfg, self.cfg["env"], self.cfg["robot"]
         asset = robot.get("asset", {}).get("assetFileName", "mjcf/smpl_humanoid.xml")
         self.model = load_model(cfg.get("model_asset", f"{self.humanoid_type}_humanoid"))
         assert self.model.body_names == self._body_names, f"asset {asset} does not have the body order of robot.body_names"
@@ -225,9 +234,6 @@ class HumanoidIm:
             # gains / default pose / torque limit live in the reference's task code (humanoid.py:1112-1121,1016-1022)
             self._robot_consts = robots.ROBOTS[self.humanoid_type]
             robots.apply_robot_gains(self.model, self._robot_consts, env.get("pd_v", 1))
-            self.p_gains = torch.tensor(self._robot_consts["p_gains"][env.get("pd_v", 1)], dtype=torch.float32, device=self.device)
-            self.d_gains = torch.tensor(self._robot_consts["d_gains"][env.get("pd_v", 1)], dtype=torch.float32, device=self.device)
-            self.default_dof_pos = torch.tensor([self._robot_consts["default_dof_pos"]], dtype=torch.float32, device=self.device)
         robots.apply_collision_filter(self.model, self.humanoid_type)   # humanoid.py:1205-1226
         self.num_bodies, self.num_dof = self.model.num_bodies, self.model.num_dof
         # ---- per-env body shapes (humanoid.py:726-766,824-866): env i wears gender_betas[i % K].  The reference writes one MJCF per env
@@ -253,26 +259,37 @@ class HumanoidIm:
                     loaded[a] = load_model(a)
                     robots.apply_collision_filter(loaded[a], self.humanoid_type)
                 self.shape_models.append(loaded[a])
-            self._env_shape = (torch.arange(self.num_envs, dtype=torch.int32) % len(self.shape_models)).to(self.device)
+            self._env_shape = torch.arange(self.num_envs, dtype=torch.int32) % len(self.shape_models)   # (on the host until _upload_model)
         K = len(self.shape_models)
         trees = [SkeletonTree(m.body_names, m.parent, m.local_translation) for m in self.shape_models]
         self.skeleton_trees = [trees[i % K] for i in range(self.num_envs)]
-        if K > 1:
-            ints, floats = pack_shapes(self.shape_models, self._kp_scale, self._kd_scale)
-        else:
-            ints, floats = self.model.pack(self._kp_scale, self._kd_scale)
-        self._model_ints = torch.from_numpy(ints).to(self.device)
-        self._model_floats = torch.from_numpy(floats).to(self.device)
-        self._model_struct = abi.model_struct(self._model_ints, self._model_floats, self.num_bodies, self.num_dof,
-                                              self.model.max_level, max(len(m.contact_body) for m in self.shape_models),
-                                              num_shapes=K)
+        self._up["ints"], self._up["floats"] = (pack_shapes(self.shape_models, self._kp_scale, self._kd_scale) if K > 1 else
+                                                self.model.pack(self._kp_scale, self._kd_scale))
         self.humanoid_masses = [self.shape_models[i % K].total_mass for i in range(min(self.num_envs, 10))]
         groups = robot.get("limb_weight_group", []) if self._is_robot else (
             ['L_Hip', 'L_Knee', 'L_Ankle', 'L_Toe'], ['R_Hip', 'R_Knee', 'R_Ankle', 'R_Toe'],
             ['Pelvis', 'Torso', 'Spine', 'Chest', 'Neck', 'Head'], ['L_Thorax', 'L_Shoulder', 'L_Elbow', 'L_Wrist', 'L_Hand'],
             ['R_Thorax', 'R_Shoulder', 'R_Elbow', 'R_Wrist', 'R_Hand'])
         self.limb_weight_group = [[self._body_names.index(g) for g in grp] for grp in groups]
-        lw = torch.from_numpy(np.stack([m.limb_lengths_and_weights(self.limb_weight_group) for m in self.shape_models])).to(self.device)
+        lw = self._up["limb_weights"] = np.stack([m.limb_lengths_and_weights(self.limb_weight_group) for m in self.shape_models])
+        self._up["gender_betas"] = gender_betas
+        # widths of the constant per-env observation columns `_upload_model` builds: 11 of the 17 shape columns, the limb lengths and weights
+        self._self_obs_extra_cols = 11 * bool(self._has_shape_obs) + lw.shape[1] * bool(self._has_limb_weight_obs)
+        self._amp_obs_extra_cols = 11 * bool(self._has_shape_obs_disc) + lw.shape[1] * bool(self._has_limb_weight_obs_disc)
+
+    def _upload_model(self):
+        if self._is_robot:
+            self.p_gains = torch.tensor(self._robot_consts["p_gains"][self.cfg["env"].get("pd_v", 1)], dtype=torch.float32, device=self.device)
+            self.d_gains = torch.tensor(self._robot_consts["d_gains"][self.cfg["env"].get("pd_v", 1)], dtype=torch.float32, device=self.device)
+            self.default_dof_pos = torch.tensor([self._robot_consts["default_dof_pos"]], dtype=torch.float32, device=self.device)
+        if self._env_shape is not None:
+            self._env_shape = self._env_shape.to(self.device)
+        K = len(self.shape_models)
+        self._model_ints = torch.from_numpy(self._up["ints"]).to(self.device)
+        self._model_floats = torch.from_numpy(self._up["floats"]).to(self.device)
+        self._model_struct = abi.model_struct(self._model_ints, self._model_floats, self.num_bodies, self.num_dof, self.model.max_level,
+                                              max(len(m.contact_body) for m in self.shape_models), num_shapes=K)
+        lw, gender_betas = torch.from_numpy(self._up["limb_weights"]).to(self.device), self._up["gender_betas"]
         shape_of_env = torch.arange(self.num_envs, device=self.device) % K
         self.humanoid_limb_and_weights = lw[shape_of_env].contiguous()
         self.humanoid_shapes = torch.from_numpy(gender_betas).to(self.device)[shape_of_env % len(gender_betas)].contiguous()   # [N, 17]
@@ -284,20 +301,17 @@ class HumanoidIm:
         self._self_obs_extra = torch.cat(se, dim=-1).float().contiguous() if se else None
         self._amp_obs_extra = torch.cat(ae, dim=-1).float().contiguous() if ae else None
 
-        # ---- _setup_character_props (humanoid.py:636-706, humanoid_amp.py:290-329) ----
+    # ---- host phase: _setup_character_props (humanoid.py:636-706, humanoid_amp.py:290-329) ----
+    def _setup_character_props(self):
+        env, robot = self.cfg["env"], self.cfg["robot"]
         self._dof_body_ids = np.arange(1, len(self._body_names))
+        nj = len(self._dof_names)
         if self._is_robot:  # humanoid.py:684-687: one DoF per joint
-            self._dof_obs_size = len(self._dof_names)
-            self._dof_offsets = np.arange(len(self._dof_names) + 1)
-            self._dof_size = len(self._dof_names)
+            self._dof_obs_size, self._dof_size, self._dof_offsets = nj, nj, np.arange(nj + 1)
         else:
-            self._dof_offsets = np.linspace(0, len(self._dof_names) * 3, len(self._body_names)).astype(int)
-            self._dof_obs_size = len(self._dof_names) * 6
-            self._dof_size = len(self._dof_names) * 3
+            self._dof_obs_size, self._dof_size, self._dof_offsets = nj * 6, nj * 3, np.linspace(0, nj * 3, len(self._body_names)).astype(int)
         self._num_actions = self._dof_size
-        self._num_self_obs = 1 + len(self._body_names) * (3 + 6 + 3 + 3) - 3
-        if self._self_obs_extra is not None:   # humanoid.py:669-676
-            self._num_self_obs += self._self_obs_extra.shape[1]
+        self._num_self_obs = 1 + len(self._body_names) * (3 + 6 + 3 + 3) - 3 + self._self_obs_extra_cols   # (the extra columns: humanoid.py:669-676)
         if not self._root_height_obs:
             self._num_self_obs -= 1
         if self.amp_obs_v == 2 and self._is_robot:
@@ -311,19 +325,18 @@ class HumanoidIm:
         if self._remove_disc_rot and (self._is_robot or not self._has_dof_subset):
             raise NotImplementedError("remove_disc_rot empties dof_subset, which only the SMPL family with robot.has_dof_subset reads (humanoid.py:405-413, "
                                       "humanoid_amp.py:996-998)")
-        track_slot, reset_mask, key_ids, amp_slot, n_amp_joints = abi.task_index_tables(
+        *self._up["tab"], self._n_amp_joints = abi.task_index_tables(   # (track_slot, reset_mask, key_ids, amp_slot), joints in the AMP observation
             self.model, self._track_bodies, self._reset_bodies, self.key_bodies, has_dof_subset=self._has_dof_subset and not self._is_robot,
             **({"amp_remove_names": tuple(self._body_names_orig)} if self._remove_disc_rot else {}))
         if self._is_robot:  # humanoid_amp.py:315-322: [root_h, root_rot 6, root_vel 3, root_ang_vel 3, dof_pos, dof_vel, key_body_pos]
             self._num_amp_obs_per_step = 13 + self._dof_obs_size + len(self._dof_names) + 3 * len(self.key_bodies) - (0 if self._amp_root_height_obs else 1)
             self.dof_subset = torch.tensor([]).long()
         else:
-            self._num_amp_obs_per_step = 13 + n_amp_joints * 9 + 3 * len(self.key_bodies) - (0 if self._amp_root_height_obs else 1)
+            self._num_amp_obs_per_step = 13 + self._n_amp_joints * 9 + 3 * len(self.key_bodies) - (0 if self._amp_root_height_obs else 1)
             if self.amp_obs_v == 2:   # + key-body velocities (humanoid_amp.py:303)
                 self._num_amp_obs_per_step += 3 * len(self.key_bodies)
-            if self._amp_obs_extra is not None:   # humanoid_amp.py:310-313
-                self._num_amp_obs_per_step += self._amp_obs_extra.shape[1]
-            dof_sub = [np.arange(3 * (j - 1), 3 * j) for j in range(1, self.num_bodies) if amp_slot[j] >= 0]
+            self._num_amp_obs_per_step += self._amp_obs_extra_cols   # humanoid_amp.py:310-313
+            dof_sub = [np.arange(3 * (j - 1), 3 * j) for j in range(1, self.num_bodies) if self._up["tab"][3][j] >= 0]
             self.dof_subset = torch.from_numpy(np.concatenate(dof_sub)) if self._has_dof_subset and dof_sub else torch.tensor([]).long()
         # env.enableHistObs (humanoid_amp.py:327-328,546-557): HumanoidAMP._compute_humanoid_obs appends `_amp_obs_buf` -- flattened, newest frame first, AS
         # IT STANDS when the observation is formed: post_physics_step (:193-204) and _reset_envs (:378-385) both form the observation BEFORE they
@@ -336,15 +349,18 @@ class HumanoidIm:
                 raise NotImplementedError("enableHistObs with self_obs_v=2: get_self_obs_size (humanoid.py:513-514) multiplies the widened block by the "
                                           "number of past states, which the observation function does not produce")
             self._hist_obs_cols = int(env.get("numAMPObsSteps", 10)) * self._num_amp_obs_per_step
-            hist = torch.zeros((self.num_envs, self._hist_obs_cols), dtype=torch.float32, device=self.device)
-            self._self_obs_extra = hist if self._self_obs_extra is None else torch.cat([self._self_obs_extra, hist], dim=-1).contiguous()
             self._num_self_obs += self._hist_obs_cols
         # extended bodies of the full-body reward (humanoid_im.py:74-82)
-        ext = list(robot.get("extend_config", [])) if self._is_robot else []
-        self.num_extend_bodies = len(ext)
+        self._up["ext"] = list(robot.get("extend_config", [])) if self._is_robot else []
+        self.num_extend_bodies = len(self._up["ext"])
+
+    def _upload_character_props(self):
+        if self._hist_obs_cols:
+            hist = torch.zeros((self.num_envs, self._hist_obs_cols), dtype=torch.float32, device=self.device)
+            self._self_obs_extra = hist if self._self_obs_extra is None else torch.cat([self._self_obs_extra, hist], dim=-1).contiguous()
+        ext = self._up["ext"]
         self.extend_body_parent_ids = self._build_key_body_ids_tensor([e["parent_name"] for e in ext]) if ext else None
-        self.extend_body_pos_in_parent = (torch.tensor([e["pos"] for e in ext], dtype=torch.float32, device=self.device).repeat(self.num_envs, 1, 1)
-                                          if ext else None)
+        self.extend_body_pos_in_parent = torch.tensor([e["pos"] for e in ext], dtype=torch.float32, device=self.device).repeat(self.num_envs, 1, 1) if ext else None
         self._ext_parent_i32 = self.extend_body_parent_ids.to(torch.int32).contiguous() if ext else None
         self._ext_offset_f32 = self.extend_body_pos_in_parent[0].contiguous() if ext else None
         self._track_bodies_id = self._build_key_body_ids_tensor(self._track_bodies)
@@ -352,9 +368,11 @@ class HumanoidIm:
         self._full_track_bodies_id = self._build_key_body_ids_tensor(self._full_track_bodies)
         self._eval_track_bodies_id = self._build_key_body_ids_tensor(self._eval_bodies)
         self._key_body_ids = self._build_key_body_ids_tensor(self.key_bodies)
-        self._contact_body_ids = self._build_key_body_ids_tensor(env["contact_bodies"])
+        self._contact_body_ids = self._build_key_body_ids_tensor(self.cfg["env"]["contact_bodies"])
 
-        # ---- BaseTask buffers (base_task.py:62-117) ----
+    # ---- host phase: the sizes of BaseTask (base_task.py:62-117), phc_sim_params_t, whether external wrenches can act ----
+    def _setup_sim_params(self):
+        cfg, env = self.cfg, self.cfg["env"]
         self.control_freq_inv = cfg["control"].get("decimation", 2)
         sim_cfg = cfg["sim"]
         step_dt = sim_cfg["physx"]["step_dt"]
@@ -365,6 +383,51 @@ class HumanoidIm:
         self.num_actions = self.get_action_size()
         cfg["env"]["numObservations"] = self.num_obs
         cfg["env"]["numActions"] = self.num_actions
+        physx = sim_cfg["physx"]
+        plane = env.get("plane", {})
+        solver = cfg.get("solver", {})  # phc_amd-specific knobs of the penalty contact model (not in the reference)
+        self._sim_params = abi.sim_params_struct(
+            sim_dt=self.sim_dt, substeps=int(sim_cfg.get("substeps", 2)), control_freq_inv=self.control_freq_inv, gravity_z=-9.81,
+            contact_stiffness=float(solver.get("contact_stiffness", 1.0e5)), contact_damping=float(solver.get("contact_damping", 1.0e3)),
+            friction=float(plane.get("dynamicFriction", 1.0)), friction_viscous=float(solver.get("friction_viscous", 2.0e3)),
+            angular_damping=0.01, max_angular_velocity=100.0, contact_offset=float(physx.get("contact_offset", 0.02)),
+            # `pd` (robot_control.yaml): explicit torque per simulate call; solver.pd_damping "continuous" (default, mode 2: only the
+            # spring term is held) or "held" (mode 1: the reference's letter, unstable on unloaded light links -- DESIGN.md)
+            control_mode=0 if self.control_mode == "isaac_pd" else (1 if solver.get("pd_damping", "continuous") == "held" else 2),
+            limit_stiffness=float(solver.get("joint_limit_stiffness", 2000.0 if self._is_robot else 0.0)),
+            limit_damping=float(solver.get("joint_limit_damping", 20.0 if self._is_robot else 0.0)),
+            lane_mapping=int(solver.get("lane_mapping", 0)),
+            # body-body contact between non-adjacent links (robot.has_self_collision, on in the shipped robot yamls)
+            self_collision=int(bool(solver.get("self_collision", self._has_self_collision))),
+            self_stiffness_scale=float(solver.get("self_stiffness_scale", 0.25)), self_damping_ratio=float(solver.get("self_damping_ratio", 0.5)),
+            force_sensor_bodies=[self._body_names.index(b) for b in self.force_sensor_joints] if self.self_obs_v == 3 else (),
+            # ground-contact model: `+solver.contact=tgs` (alias rigid) = the velocity-level rigid contact with what parse_sim_params hands PhysX
+            # (run_hydra.py:88-91, sim/default_sim.yaml: num_position_iterations, max_depenetration_velocity, bounce_threshold_velocity; plane
+            # restitution of the env yaml); default `penalty` (include/phc_amd.h, ABI 34)
+            contact_model=str(solver.get("contact", "penalty")), contact_iterations=int(solver.get("contact_iterations", physx.get("num_position_iterations", 4))),
+            contact_impedance=float(solver.get("contact_impedance", 1.0e5)),
+            max_depenetration_velocity=float(physx.get("max_depenetration_velocity", 10.0)),
+            bounce_threshold_velocity=float(physx.get("bounce_threshold_velocity", 0.2)), restitution=float(plane.get("restitution", 0.0)),
+            # `solver.inertia_lag` (ABI 35): the sub-steps behind the first one of a simulate() call keep its articulated inertias and only redo the bias-force recursion.
+            # Round 6: the DEFAULT for the penalty contact model (stepper -5 %; H1 -10 %, G1 -11 %) -- pinned like the fresh scheme since
+            # tests/test_stepper_options.py::test_stepper_equals_the_double_precision_recursion; `+solver.inertia_lag=0` = every sub-step fresh.  The rigid model
+            # (`+solver.contact=tgs`) re-solves every sub-step with fresh impedances and runs fresh.
+            # `+solver.force_average=1` publishes contact_force / dof_force as means over the env step's sub-steps instead of the last one's values
+            inertia_lag=int(bool(solver.get("inertia_lag", str(solver.get("contact", "penalty")) == "penalty"))), force_average=int(bool(solver.get("force_average", 0))))
+        if self._sim_params.contact_model == 1 and max((int(c) for c in np.bincount(self.model.contact_body, minlength=1)), default=0) > 32:
+            # (the rigid model's per-point active / released sets are 32-bit masks: a point beyond bit 31 could never be released)
+            raise ValueError("solver.contact=tgs supports at most 32 ground-contact points per body; this model has more (use the penalty model)")
+
+        # ---- external wrenches (gym.apply_rigid_body_force_tensors; phc_sim_step_wrench) and the push schedule `+perturb.*` (phc_amd/perturb.py):
+        # refused here, on host facts; the schedule's buffers are made with the task's (_allocate_buffers) ----
+        self._ext_force = self._ext_torque = None   # [N, NB, 3] buffers of the one-shot API, made at its first call
+        self._ext_pending = None                    # (force given, torque given, sim_calls) for the next step() only
+        self._push = None
+        if cfg.get("perturb", None):
+            self._check_wrench_supported("perturb")
+
+    # ---- device phase: BaseTask buffers (base_task.py:62-117) ----
+    def _allocate_buffers(self):
         N, dev = self.num_envs, self.device
         f32 = dict(device=dev, dtype=torch.float32)
         i64 = dict(device=dev, dtype=torch.long)
@@ -376,8 +439,7 @@ class HumanoidIm:
         self.randomize_buf = torch.zeros(N, **i64)
         self.extras = {}
         self._eval_acc = None   # state of an open device metric accumulation (begin_eval_accumulation)
-        self.viewer = None
-        self.paused = False
+        self.viewer, self.paused = None, False
 
         # ---- _setup_tensors (humanoid.py:179-247): Isaac Gym layouts ----
         NB, D = self.num_bodies, self.num_dof
@@ -404,59 +466,20 @@ class HumanoidIm:
         self._pd_target = torch.zeros((N, D), **f32)
         self._terminate_buf = torch.ones(N, **i64)
         # S6 (gym.acquire_force_sensor_tensor, humanoid.py:183-190): [N, S*6], force then torque per sensor in the sensor body's frame
-        sensors_on = self.self_obs_v == 3 and not self._is_robot
-        self.vec_sensor_tensor = torch.zeros((N, 6 * len(self.force_sensor_joints)), **f32) if sensors_on else None
+        self.vec_sensor_tensor = torch.zeros((N, 6 * len(self.force_sensor_joints)), **f32) if self.self_obs_v == 3 else None
         self._sim_struct = abi.sim_state_struct(N, self._root_states, self._dof_state, self._rigid_body_state, self._contact_forces,
                                                 self.dof_force_tensor, self._pd_target, force_sensor=self.vec_sensor_tensor,
                                                 env_shape=self._env_shape)
-        physx = sim_cfg["physx"]
-        plane = env.get("plane", {})
-        solver = cfg.get("solver", {})  # phc_amd-specific knobs of the penalty contact model (not in the reference)
-        self._sim_params = abi.sim_params_struct(
-            sim_dt=self.sim_dt, substeps=int(sim_cfg.get("substeps", 2)), control_freq_inv=self.control_freq_inv, gravity_z=-9.81,
-            contact_stiffness=float(solver.get("contact_stiffness", 1.0e5)), contact_damping=float(solver.get("contact_damping", 1.0e3)),
-            friction=float(plane.get("dynamicFriction", 1.0)), friction_viscous=float(solver.get("friction_viscous", 2.0e3)),
-            angular_damping=0.01, max_angular_velocity=100.0, contact_offset=float(physx.get("contact_offset", 0.02)),
-            # `pd` (robot_control.yaml): explicit torque per simulate call; solver.pd_damping "continuous" (default, mode 2: only the
-            # spring term is held) or "held" (mode 1: the reference's letter, unstable on unloaded light links -- DESIGN.md)
-            control_mode=0 if self.control_mode == "isaac_pd" else (1 if solver.get("pd_damping", "continuous") == "held" else 2),
-            limit_stiffness=float(solver.get("joint_limit_stiffness", 2000.0 if self._is_robot else 0.0)),
-            limit_damping=float(solver.get("joint_limit_damping", 20.0 if self._is_robot else 0.0)),
-            lane_mapping=int(solver.get("lane_mapping", 0)),
-            # body-body contact between non-adjacent links (robot.has_self_collision, on in the shipped robot yamls)
-            self_collision=int(bool(solver.get("self_collision", self._has_self_collision))),
-            self_stiffness_scale=float(solver.get("self_stiffness_scale", 0.25)), self_damping_ratio=float(solver.get("self_damping_ratio", 0.5)),
-            force_sensor_bodies=[self._body_names.index(b) for b in self.force_sensor_joints] if sensors_on else (),
-            # ground-contact model: `+solver.contact=tgs` (alias rigid) = the velocity-level rigid contact with what parse_sim_params hands PhysX
-            # (run_hydra.py:88-91, sim/default_sim.yaml: num_position_iterations, max_depenetration_velocity, bounce_threshold_velocity; plane
-            # restitution of the env yaml); default `penalty` (include/phc_amd.h, ABI 34)
-            contact_model=str(solver.get("contact", "penalty")), contact_iterations=int(solver.get("contact_iterations", physx.get("num_position_iterations", 4))),
-            contact_impedance=float(solver.get("contact_impedance", 1.0e5)),
-            max_depenetration_velocity=float(physx.get("max_depenetration_velocity", 10.0)),
-            bounce_threshold_velocity=float(physx.get("bounce_threshold_velocity", 0.2)), restitution=float(plane.get("restitution", 0.0)),
-            # `solver.inertia_lag` (ABI 35): the sub-steps behind the first one of a simulate() call keep its articulated inertias and only redo the bias-force recursion.
-            # Round 6: the DEFAULT for the penalty contact model (stepper -5 %; H1 -10 %, G1 -11 %) -- pinned like the fresh scheme since
-            # tests/test_stepper_options.py::test_stepper_equals_the_double_precision_recursion; `+solver.inertia_lag=0` = every sub-step fresh.  The rigid model
-            # (`+solver.contact=tgs`) re-solves every sub-step with fresh impedances and runs fresh.
-            # `+solver.force_average=1` publishes contact_force / dof_force as means over the env step's sub-steps instead of the last one's values
-            inertia_lag=int(bool(solver.get("inertia_lag", str(solver.get("contact", "penalty")) == "penalty"))), force_average=int(bool(solver.get("force_average", 0))))
-        if self._sim_params.contact_model == 1 and max((int(c) for c in np.bincount(self.model.contact_body, minlength=1)), default=0) > 32:
-            # (the rigid model's per-point active / released sets are 32-bit masks: a point beyond bit 31 could never be released)
-            raise ValueError("solver.contact=tgs supports at most 32 ground-contact points per body; this model has more (use the penalty model)")
-
-        # ---- external wrenches (gym.apply_rigid_body_force_tensors; phc_sim_step_wrench) and the push schedule `+perturb.*` (phc_amd/perturb.py) ----
-        self._ext_force = self._ext_torque = None   # [N, NB, 3] buffers of the one-shot API, made at its first call
-        self._ext_pending = None                    # (force given, torque given, sim_calls) for the next step() only
-        self._push = None
-        pcfg = cfg.get("perturb", None)
+        pcfg = self.cfg.get("perturb", None)
         if pcfg:
-            self._check_wrench_supported("perturb")
             from ...perturb import make_schedule
             # (`+perturb.rng=device`: one launch per step, capturable; the ranks of a multi-GPU run draw disjoint streams from one seed)
-            self._push = make_schedule(pcfg, N, list(self._body_names), self.dt, dev, default_seed=int(cfg.get("seed", 0)),
-                                       env_offset=int(cfg.get("rank", os.environ.get("RANK", 0))) * N)
+            self._push = make_schedule(pcfg, N, list(self._body_names), self.dt, dev, default_seed=int(self.cfg.get("seed", 0)),
+                                       env_offset=int(self.cfg.get("rank", os.environ.get("RANK", 0))) * N)
 
-        # ---- action scaling (A1) + freeze masks (humanoid.py:1331-1409,1549-1554) ----
+    # ---- device phase: action scaling (A1) + freeze masks (humanoid.py:1331-1409,1549-1554) ----
+    def _setup_action_scaling(self):
+        dev, D = self.device, self.num_dof
         self.dof_limits_lower, self.dof_limits_upper = (torch.from_numpy(x).to(dev) for x in self.model.dof_limits())
         self.dof_limits = torch.stack([self.dof_limits_lower, self.dof_limits_upper], dim=-1)
         self.torque_limits = torch.from_numpy(self.model.dof_effort.astype(np.float32)).to(dev)
@@ -470,7 +493,7 @@ class HumanoidIm:
             # torques = p_gains * (actions * action_scale + default_dof_pos - dof_pos) - d_gains * dof_vel (humanoid.py:1585-1590):
             # the PD target the stepper sees is default_dof_pos + action_scale * clip(action, +-10)
             self._torque_target_offset = self.default_dof_pos[0].contiguous()
-            self._torque_target_scale = torch.full((D,), float(cfg["control"].get("action_scale", 1.0)), **f32)
+            self._torque_target_scale = torch.full((D,), float(self.cfg["control"].get("action_scale", 1.0)), device=dev, dtype=torch.float32)
         freeze = np.zeros(D, dtype=np.int32)
         for names, on in ((("L_Hand", "R_Hand"), self._freeze_hand), (("L_Toe", "R_Toe"), self._freeze_toe)):
             if on and not self._is_robot:
@@ -478,9 +501,29 @@ class HumanoidIm:
                     i = self._dof_names.index(n) * 3
                     freeze[i:i + 3] = 1
         self._freeze_mask = torch.from_numpy(freeze).to(dev)
-        self.actions = torch.zeros((N, self.num_actions), **f32)
+        self.actions = torch.zeros((self.num_envs, self.num_actions), device=dev, dtype=torch.float32)
 
-        # ---- termination (humanoid.py:708-724, humanoid_im.py:539-543) ----
+    # ---- host phase: options of HumanoidAMP / HumanoidIm (humanoid_amp.py:109-136, humanoid_im.py:71-123) ----
+    def _setup_im_options(self):
+        env = self.cfg["env"]
+        # draws behind the random reference offsets of zero_out_far_train (reset, clip restart) / cycle_motion_xp (clip restart)
+        self._far_start = bool(self.zero_out_far and self.zero_out_far_train)
+        if self.zero_out_far and self._track_bodies[0] != self._body_names[0]:
+            raise NotImplementedError("zero_out_far needs the root as the first track body (humanoid_im.py:785)")
+        # env.occl_training (humanoid.py:324-325, humanoid_im.py:96-97): per-env occlusion of tracked bodies, read by the task kernels
+        self._occl_training = bool(env.get("occl_training", False))
+        self._occl_training_prob = float(env.get("occl_training_prob", 0.1))
+        if self._occl_training and (list(self._track_bodies) != list(self._body_names) or self._num_traj_samples > 1):
+            raise NotImplementedError("occl_training: the reference indexes the mask by body id and by env row (humanoid_im.py:800,1181): "
+                                      "full-body tracking, without fut_tracks")
+        # env.res_action (humanoid.py:327, humanoid_im.py:1094-1099): actions are residuals on the reference pose of the next frame
+        self._res_action = bool(env.get("res_action", False))
+
+    # ---- device phase: termination (humanoid.py:708-724, humanoid_im.py:539-543) ----
+    def _allocate_im_state(self):
+        env, N, dev, NB, D = self.cfg["env"], self.num_envs, self.device, self.num_bodies, self.num_dof
+        f32 = dict(device=dev, dtype=torch.float32)
+        i64 = dict(device=dev, dtype=torch.long)
         self._termination_heights = torch.full((NB,), float(env["terminationHeight"]), **f32)
         if "Head" in self._body_names:
             self._termination_heights[self._body_names.index("Head")] = max(0.3, float(env["terminationHeight"]))
@@ -497,20 +540,13 @@ class HumanoidIm:
         self._reset_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
         self._reset_counter = 0
         self._launch_events = None   # see step()
-        # device-built list of the envs that finished in the last step (phc_im_buffers_t.reset_list): reset_done() works on it
-        self._use_reset_list = getattr(self, "_use_reset_list", True)
         self._reset_list = torch.zeros(abi.RESET_SUBLISTS * abi.reset_sublist_cap(N), device=dev, dtype=torch.int32) if self._use_reset_list else None
         self._reset_count = torch.zeros((3, abi.RESET_SUBLISTS, abi.RESET_COUNT_STRIDE), device=dev, dtype=torch.int32) if self._use_reset_list else None
         self._reset_slot, self._reset_list_pending = 0, False
         self._reset_rng_dev = torch.zeros(1, device=dev, dtype=torch.int64)   # phc_im_buffers_t.reset_rng_counter (advanced by the post-physics launch)
         self._cycle_phase = torch.zeros(N, **f32) if self.cycle_motion else None
-        # draws behind the random reference offsets of zero_out_far_train (reset, clip restart) / cycle_motion_xp (clip restart)
-        self._far_start = bool(self.zero_out_far and self.zero_out_far_train)
         self._offset_rand = torch.zeros((N, 2), **f32) if (self._far_start or (self.cycle_motion and self.cycle_motion_xp)) else None
-        if not hasattr(self, "_recovery_counter"):
-            self._recovery_counter = None                        # HumanoidImGetup owns one
-        if self.zero_out_far and self._track_bodies[0] != self._body_names[0]:
-            raise NotImplementedError("zero_out_far needs the root as the first track body (humanoid_im.py:785)")
+        self._recovery_counter = None                            # HumanoidImGetup extends this phase with one
         S, A = self._num_amp_obs_steps, self._num_amp_obs_per_step
         # AMP history (humanoid_amp.py:125-131): every env owns a strip of 2 S frames; the history is the window of S frames starting at
         # row `_amp_head` (newest first, like `_amp_obs_buf` of the reference).  A step writes its frame in the row BEFORE the window and
@@ -527,31 +563,18 @@ class HumanoidIm:
         self.ref_body_vel = torch.zeros((N, NB, 3), **f32)
         self.ref_body_rot = torch.zeros((N, NB, 4), **f32)
         self.ref_dof_pos = torch.zeros((N, D), **f32)
-        # env.occl_training (humanoid.py:324-325, humanoid_im.py:96-97): per-env occlusion of tracked bodies, read by the task kernels
-        self._occl_training = bool(env.get("occl_training", False))
-        self._occl_training_prob = float(env.get("occl_training_prob", 0.1))
         self._occl_mask = None
         if self._occl_training:
-            if list(self._track_bodies) != list(self._body_names) or self._num_traj_samples > 1:
-                raise NotImplementedError("occl_training: the reference indexes the mask by body id and by env row (humanoid_im.py:800,1181): "
-                                          "full-body tracking, without fut_tracks")
             J = len(self._track_bodies)
             self.random_occlu_idx = torch.zeros((N, J), dtype=torch.bool, device=dev)
             self.random_occlu_count = torch.zeros((N, J), **i64)
             self._occl_mask = torch.zeros((N, J), dtype=torch.uint8, device=dev)
-        # env.res_action (humanoid.py:327, humanoid_im.py:1094-1099): actions are residuals on the reference pose of the next frame
-        self._res_action = bool(env.get("res_action", False))
         if self._res_action:
             self._sim_struct.pd_ref = abi.ptr(self.ref_dof_pos)
         self.ref_motion_cache = {}
-        self._tab = [torch.from_numpy(t).to(dev) for t in (track_slot, reset_mask, key_ids, amp_slot)]
-        self._n_amp_joints = n_amp_joints
+        self._tab = [torch.from_numpy(t).to(dev) for t in self._up["tab"]]
         self._im_params = None
         self._rebuild_im_params()
-
-        # ---- reference motions (humanoid_im.py:316-367) ----
-        self._load_motion(env["motion_file"])
-        return
 
     # ------------------------------------------------------------------ small helpers
     def _build_key_body_ids_tensor(self, names):
@@ -682,19 +705,10 @@ class HumanoidIm:
 
     def get_task_obs_size_detail(self):
         """humanoid_im.py:522-537."""
-        d = OrderedDict()
-        d["target"] = self.get_task_obs_size()
-        d["fut_tracks"] = self._fut_tracks
-        d["num_traj_samples"] = self._num_traj_samples
-        d["obs_v"] = self.obs_v
-        d["track_bodies"] = self._track_bodies
-        d["models_path"] = self.models_path
         env = self.cfg["env"]
-        d["num_prim"] = env.get("num_prim", 2)
-        d["training_prim"] = env.get("training_prim", 1)
-        d["actors_to_load"] = env.get("actors_to_load", 2)
-        d["has_lateral"] = env.get("has_lateral", True)
-        return d
+        return OrderedDict(target=self.get_task_obs_size(), fut_tracks=self._fut_tracks, num_traj_samples=self._num_traj_samples, obs_v=self.obs_v,
+                           track_bodies=self._track_bodies, models_path=self.models_path, num_prim=env.get("num_prim", 2),
+                           training_prim=env.get("training_prim", 1), actors_to_load=env.get("actors_to_load", 2), has_lateral=env.get("has_lateral", True))
 
     def get_states(self):
         return self.states_buf
@@ -702,47 +716,10 @@ class HumanoidIm:
     # ------------------------------------------------------------------ motions
     def _load_motion(self, motion_train_file, motion_test_file=[]):
         assert self._dof_offsets[-1] == self.num_dof
-        mf = motion_train_file
-        if isinstance(mf, str) and mf.startswith("stand") and not self._is_robot:
-            # "stand[:seconds]" -- the rest pose standing still (a physically feasible clip for end-to-end sanity runs)
-            from ...utils.synthetic_motion import make_stand_clip
-            mf = {"stand_00000": make_stand_clip(self.model, float(mf.split(":")[1]) if ":" in mf else 10.0)}
-        if isinstance(mf, str) and mf.split(":")[0] in ("stand", "armswing") and self._is_robot:
-            # robots: "stand[:seconds]" / "armswing[:seconds]" -- the default joint pose standing still / with swinging shoulder-pitch joints (round 5)
-            from ...utils.synthetic_motion import make_robot_stand_clip
-            from ...robots import ROBOTS
-            kind = mf.split(":")[0]
-            mf = {f"{kind}_00000": make_robot_stand_clip(self.model, ROBOTS[self.humanoid_type]["default_dof_pos"], float(mf.split(":")[1]) if ":" in mf else 10.0,
-                                                        num_extend=self.num_extend_bodies, arm_swing=0.5 if kind == "armswing" else 0.0)}
-        if isinstance(mf, str) and mf.split(":")[0] in ("squat", "stepinplace", "walk") and not self._is_robot:
-            # "squat | stepinplace | walk[:seconds]" -- locomotion-class sanity clips (leg IK on prescribed pelvis / foot trajectories: feet leave the
-            # ground and come back without sliding, the walk translates the centre of mass at 0.7 m/s)
-            from ...utils.synthetic_motion import make_gait_clip
-            kind = mf.split(":")[0]
-            mf = {f"{kind}_00000": make_gait_clip(self.model, kind, float(mf.split(":")[1]) if ":" in mf else 10.0)}
-        if isinstance(mf, str) and mf.startswith("armswing") and not self._is_robot:
-            # "armswing[:seconds]" -- standing with swinging arms (the second feasible sanity clip)
-            from ...utils.synthetic_motion import make_armswing_clip
-            mf = {"armswing_00000": make_armswing_clip(self.model, float(mf.split(":")[1]) if ":" in mf else 10.0)}
-        if isinstance(mf, str) and mf.startswith("locomotion") and not self._is_robot:
-            # "locomotion[:num_clips[:seed[:seconds]]]" -- a multi-clip set of feasible stand / arm-swing / step-in-place / walk (/ squat) clips (round 5)
-            from ...utils.synthetic_motion import make_locomotion_library
-            parts = mf.split(":")
-            mf = make_locomotion_library(self.model, int(parts[1]) if len(parts) > 1 else 64, int(parts[2]) if len(parts) > 2 else 0,
-                                         float(parts[3]) if len(parts) > 3 else 8.0)
-        if isinstance(mf, str) and mf.startswith("synthetic"):
-            # "synthetic[:num_clips[:seed[:mean_seconds]]]" -- AMASS-shaped smooth random clips
-            parts = mf.split(":")
-            nclips = int(parts[1]) if len(parts) > 1 else 1
-            seed = int(parts[2]) if len(parts) > 2 else 0
-            mean_s = float(parts[3]) if len(parts) > 3 else 8.0
-            min_frames = max(30, int(self._min_motion_len) if self._min_motion_len > 0 else 30)
-            if self._is_robot:
-                mf = make_robot_motion_dict(self.model, nclips, seed=seed, mean_seconds=mean_s, num_extend=self.num_extend_bodies, min_frames=min_frames)
-            else:
-                from ...utils.synthetic_motion import BASE_ROT
-                mf = make_motion_dict(self.model.parent, nclips, seed=seed, body_names=self._body_names, mean_seconds=mean_s, min_frames=min_frames,
-                                      base_rot=None if self._has_upright_start else BASE_ROT)
+        # (a synthetic clip spec -- `stand:5`, `synthetic:3:1`, ... -- becomes its motion dict; a path or a dict is handed on as it is)
+        mf = motion_from_spec(motion_train_file, self.model, self._is_robot, self._robot_consts["default_dof_pos"] if self._is_robot else None,
+                              num_extend=self.num_extend_bodies, min_frames=max(30, int(self._min_motion_len) if self._min_motion_len > 0 else 30),
+                              base_rot=None if self._has_upright_start else BASE_ROT)
         from ...config import EasyDict
         motion_lib_cfg = EasyDict({"motion_file": mf, "device": self.device, "fix_height": FixHeightMode.full_fix,
                                    "min_length": self._min_motion_len, "max_length": -1, "im_eval": flags.im_eval,
@@ -750,18 +727,12 @@ class HumanoidIm:
                                    "heading_rng": self.cfg["env"].get("heading_rng", "persistent"),
                                    "rank": int(self.cfg.get("rank", os.environ.get("RANK", 0)))})   # per-rank heading / crop stream (run_hydra.py:121 seeds per rank)
         if self._is_robot:  # humanoid_im.py:342-359
-            motion_lib_cfg["robot"] = self.cfg["robot"]
-            motion_lib_cfg["robot_model"] = self.model
-            self._motion_lib_cls = MotionLibReal
-        else:
-            self._motion_lib_cls = MotionLibSMPL
+            motion_lib_cfg["robot"], motion_lib_cfg["robot_model"] = self.cfg["robot"], self.model
+        self._motion_lib_cls = MotionLibReal if self._is_robot else MotionLibSMPL
         self._motion_train_lib = self._motion_lib_cls(motion_lib_cfg)
         self._motion_eval_lib = None  # built lazily by get_eval_motion_lib()
         self._motion_lib = self._motion_train_lib
-        self._motion_lib.load_motions(skeleton_trees=self.skeleton_trees, gender_betas=self.humanoid_shapes.cpu(),
-                                      limb_weights=self.humanoid_limb_and_weights.cpu(),
-                                      random_sample=(not flags.test) and (not self.seq_motions),
-                                      max_len=-1 if flags.test else self.max_len, start_idx=self.start_idx)
+        self._reload_motions(start_idx=self.start_idx)
 
     def get_eval_motion_lib(self):
         """The reference's `_motion_eval_lib` (humanoid_im.py:333-336): same data, `im_eval=True` -> clips sorted by length."""
@@ -776,15 +747,13 @@ class HumanoidIm:
     def begin_seq_motion_samples(self):
         """humanoid_im.py:468-472."""
         self.start_idx = 0
-        self._motion_lib.load_motions(skeleton_trees=self.skeleton_trees, gender_betas=self.humanoid_shapes.cpu(),
-                                      limb_weights=self.humanoid_limb_and_weights.cpu(), random_sample=False, start_idx=self.start_idx)
+        self._load_motions(random_sample=False, start_idx=self.start_idx)
         self.reset()
 
     def forward_motion_samples(self):
         """humanoid_im.py:474-477."""
         self.start_idx += self.num_envs
-        self._motion_lib.load_motions(skeleton_trees=self.skeleton_trees, gender_betas=self.humanoid_shapes.cpu(),
-                                      limb_weights=self.humanoid_limb_and_weights.cpu(), random_sample=False, start_idx=self.start_idx)
+        self._load_motions(random_sample=False, start_idx=self.start_idx)
         self.reset()
 
     def resample_motions(self):
@@ -792,10 +761,13 @@ class HumanoidIm:
         self._reload_motions()
         self.reset()
 
-    def _reload_motions(self):
-        self._motion_lib.load_motions(skeleton_trees=self.skeleton_trees, limb_weights=self.humanoid_limb_and_weights.cpu(),
-                                      gender_betas=self.humanoid_shapes.cpu(), random_sample=(not flags.test) and (not self.seq_motions),
-                                      max_len=-1 if flags.test else self.max_len)
+    def _reload_motions(self, **start):
+        self._load_motions(random_sample=(not flags.test) and (not self.seq_motions), max_len=-1 if flags.test else self.max_len, **start)
+
+    def _load_motions(self, **how):
+        """Every `load_motions` of the task: the envs' skeletons, shapes and limb weights, and how the call samples (`random_sample`, `max_len`, `start_idx`)."""
+        self._motion_lib.load_motions(skeleton_trees=self.skeleton_trees, gender_betas=self.humanoid_shapes.cpu(),
+                                      limb_weights=self.humanoid_limb_and_weights.cpu(), **how)
 
     # ------------------------------------------------------------------ step (base_task.py:216-234)
     def step(self, actions):
@@ -893,7 +865,7 @@ class HumanoidIm:
     def post_physics_step(self):
         if (flags.im_eval, flags.no_collision_check) != self._flag_state:
             self._rebuild_im_params()
-        new_head = self._amp_head - 1 if self._amp_head > 0 else self._num_amp_obs_steps
+        new_head = self._next_amp_head()
         amp_in, amp_out = self._amp_window(self._amp_head), self._amp_window(new_head)
         if self.cycle_motion:
             # the draw behind `_sample_time` of the envs whose clip restarts this step (humanoid_im.py:1127); one value per
@@ -964,6 +936,10 @@ class HumanoidIm:
         """Close the accumulation; -> the device tensors (failed int32 [N], sums fp64 [N, 5], count int32 [N]), or None if none was open."""
         acc, self._eval_acc = self._eval_acc, None
         return None if acc is None else (acc["failed"], acc["sums"], acc["count"])
+
+    def _next_amp_head(self):
+        """Where the window of the AMP strip stands after one more step: a row down, or back at the top half once it has reached row 0."""
+        return self._amp_head - 1 if self._amp_head > 0 else self._num_amp_obs_steps
 
     def _post_physics_host(self, new_head):
         """The HOST side of a post-physics step (no launch): the AMP window moved, a reset list is pending, the info dict.  A replayed hipGraph of a
@@ -1047,8 +1023,7 @@ class HumanoidIm:
         """Host bookkeeping of one reset_done() (`reset`) + step() whose launches a graph replay has just issued."""
         if reset:
             self._reset_done_host(self._use_reset_list and self._reset_list_pending)
-        new_head = self._amp_head - 1 if self._amp_head > 0 else self._num_amp_obs_steps
-        self._post_physics_host(new_head)
+        self._post_physics_host(self._next_amp_head())
 
     # ------------------------------------------------------------------ reset (humanoid.py:537-621)
     def reset(self, env_ids=None):
@@ -1058,10 +1033,8 @@ class HumanoidIm:
         self._reset_envs(env_ids)
         if safe_reset:
             # "simulate one step, then reset again" (humanoid.py:544-550)
-            L.check(self._lib.phc_sim_step(self._model_struct, self._sim_params, self._sim_struct, None, None, None, None, 1, _stream()),
-                    "phc_sim_step")
+            L.check(self._lib.phc_sim_step(self._model_struct, self._sim_params, self._sim_struct, None, None, None, None, 1, _stream()), "phc_sim_step")
             self._reset_envs(env_ids)
-        return
 
     def _reset_envs(self, env_ids):
         n = len(env_ids)
@@ -1070,12 +1043,7 @@ class HumanoidIm:
         env_ids = torch.as_tensor(env_ids, device=self.device).to(torch.long).contiguous()
         start_at_zero = (self._state_init == HumanoidIm.StateInit.Start) or flags.test  # humanoid_im.py:1003-1011
         phase = torch.rand(env_ids.shape, device=self.device) if self._state_init != HumanoidIm.StateInit.Start else None
-        if self._far_start:
-            torch.rand(self._offset_rand.shape, out=self._offset_rand)
-        cur = self._amp_obs_buf
-        self._refresh_hist_obs()
-        self._ensure_amp_ref_table()
-        buf = self._buffers(cur, cur)
+        buf = self._reset_prologue()
         L.check(self._lib.phc_im_reset(self._model_struct, self._motion_lib.struct, self._im_params, self._sim_struct, buf, n,
                                        env_ids.data_ptr(), abi.ptr(phase), int(bool(start_at_zero)), _stream()), "phc_im_reset")
         self._obs_noise(env_ids)
@@ -1090,19 +1058,25 @@ class HumanoidIm:
         zeroed afterwards: nothing reads reset_buf before the next post-physics launch rewrites every entry of it.  The envs come
         from the list the post-physics kernel built on the device (dense wavefronts; a masked sweep over all envs is the fallback)."""
         start_at_zero = (self._state_init == HumanoidIm.StateInit.Start) or flags.test
-        cur = self._amp_obs_buf
         use_list = self._use_reset_list and self._reset_list_pending
-        if self._far_start:
-            torch.rand(self._offset_rand.shape, out=self._offset_rand)
-        self._refresh_hist_obs()
-        self._ensure_amp_ref_table()
-        buf = self._buffers(cur, cur)
+        buf = self._reset_prologue()
         if not use_list:   # nothing appended since the last consumption (e.g. right after reset()): masked sweep over reset_buf
             buf.reset_list = None
         L.check(self._lib.phc_im_reset_done(self._model_struct, self._motion_lib.struct, self._im_params, self._sim_struct, buf,
                                             self._reset_seed, self._reset_counter + 1, int(bool(start_at_zero)), _stream()), "phc_im_reset_done")
         self._reset_done_host(use_list)
         self._obs_noise(reset_rows=True)
+
+    def _reset_prologue(self, from_state=False):
+        """In front of every reset launch: the far-start draw and the AMP reference table (not for a reset from the env's own state, which reads
+        neither), the history columns of the observation; -> the launch's buffers, AMP history written in place."""
+        if self._far_start and not from_state:
+            torch.rand(self._offset_rand.shape, out=self._offset_rand)
+        self._refresh_hist_obs()
+        if not from_state:
+            self._ensure_amp_ref_table()
+        cur = self._amp_obs_buf
+        return self._buffers(cur, cur)
 
     def _refresh_hist_obs(self):
         """env.enableHistObs: the current AMP history (the one the launch about to be issued has not touched yet) into the trailing columns of
@@ -1202,8 +1176,7 @@ class HumanoidIm:
     # ------------------------------------------------------------------ AMP demo observations (humanoid_amp.py:215-284)
     def fetch_amp_obs_demo(self, num_samples):
         if self._amp_obs_demo_buf is None:
-            self._amp_obs_demo_buf = torch.zeros((num_samples, self._num_amp_obs_steps, self._num_amp_obs_per_step),
-                                                 device=self.device, dtype=torch.float32)
+            self._amp_obs_demo_buf = torch.zeros((num_samples, self._num_amp_obs_steps, self._num_amp_obs_per_step), device=self.device, dtype=torch.float32)
         else:
             assert self._amp_obs_demo_buf.shape[0] == num_samples
         motion_ids = self._motion_lib.sample_motions(num_samples)

@@ -17,8 +17,15 @@ from .humanoid_im import HumanoidIm, _stream
 
 class HumanoidImGetup(HumanoidIm):
 
+    _use_reset_list = False   # episode kinds are decided on the host: the done envs are listed there
+
     def __init__(self, cfg, sim_params=None, physics_engine=None, device_type="cuda", device_id=0, headless=True):
-        env = cfg["env"]
+        super().__init__(cfg=cfg, sim_params=sim_params, physics_engine=physics_engine, device_type=device_type, device_id=device_id,
+                         headless=headless)
+        self._generate_fall_states()
+
+    def _load_humanoid_configs(self):
+        env = self.cfg["env"]
         self._recovery_episode_prob_tgt = self._recovery_episode_prob = env["recoveryEpisodeProb"]
         self._recovery_steps_tgt = self._recovery_steps = env["recoverySteps"]
         self._fall_init_prob_tgt = self._fall_init_prob = env["fallInitProb"]
@@ -26,16 +33,15 @@ class HumanoidImGetup(HumanoidIm):
             self._recovery_episode_prob_tgt = self._recovery_episode_prob = 1
             self._fall_init_prob_tgt = self._fall_init_prob = 0
         self.getup_udpate_epoch = env.get("getup_udpate_epoch", 10000)
-        dev = f"cuda:{device_id}"
-        n = env["num_envs"]
-        self._recovery_counter = torch.zeros(n, device=dev, dtype=torch.int)  # before super(): the kernel buffers point at it
+        self._reset_fall_env_ids = []
+        super()._load_humanoid_configs()
+
+    def _allocate_im_state(self):
+        super()._allocate_im_state()
+        n, dev = self.num_envs, self.device
+        self._recovery_counter = torch.zeros(n, device=dev, dtype=torch.int)  # (the kernel buffers point at it)
         self.availalbe_fall_states = torch.zeros(n, device=dev, dtype=torch.long)
         self.fall_id_assignments = torch.zeros(n, device=dev, dtype=torch.long)
-        self._reset_fall_env_ids = []
-        self._use_reset_list = False   # episode kinds are decided on the host: the done envs are listed there
-        super().__init__(cfg=cfg, sim_params=sim_params, physics_engine=physics_engine, device_type=device_type, device_id=device_id,
-                         headless=headless)
-        self._generate_fall_states()
 
     # ------------------------------------------------------------------ schedule (:71-78)
     def update_getup_schedule(self, epoch_num, getup_udpate_epoch=5000):
@@ -109,10 +115,8 @@ class HumanoidImGetup(HumanoidIm):
         if refresh:
             L.check(self._lib.phc_refresh_body_state_indexed(self._model_struct, self._sim_struct, n, ids.data_ptr(), _stream()),
                     "phc_refresh_body_state_indexed")
-        cur = self._amp_obs_buf
-        self._refresh_hist_obs()
         L.check(self._lib.phc_im_reset_from_state(self._model_struct, self._motion_lib.struct, self._im_params, self._sim_struct,
-                                                  self._buffers(cur, cur), n, ids.data_ptr(), int(fill_history), _stream()),
+                                                  self._reset_prologue(from_state=True), n, ids.data_ptr(), int(fill_history), _stream()),
                 "phc_im_reset_from_state")
 
     def reset_done(self):

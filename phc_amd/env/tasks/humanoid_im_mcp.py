@@ -94,8 +94,13 @@ def load_bypass_mlp(path_or_state, num_obs, num_dof, device="cpu"):
 class MCPMixin:
     """Shared by HumanoidImMCP and HumanoidImMCPGetup."""
 
-    def _mcp_config(self, cfg):
-        env = cfg["env"]
+    def __init__(self, cfg, sim_params=None, physics_engine=None, device_type="cuda", device_id=0, headless=True):
+        super().__init__(cfg=cfg, sim_params=sim_params, physics_engine=physics_engine, device_type=device_type, device_id=device_id,
+                         headless=headless)
+        self._mcp_load()
+
+    def _load_humanoid_configs(self):
+        env = self.cfg["env"]
         self.num_prim = env.get("num_prim", 3)
         self.discrete_mcp = env.get("discrete_moe", False)
         self.has_pnn = env.get("has_pnn", False)
@@ -104,6 +109,7 @@ class MCPMixin:
         self.mlp_bypass = env.get("mlp_bypass", False)           # humanoid.py:338-341: a distilled MLP acts in place of the mixed primitives
         self.mlp_model_path = env.get("mlp_model_path", "")
         self.mlp_model = None
+        super()._load_humanoid_configs()
 
     def _mcp_load(self):
         self.pnn, self.actors = None, None
@@ -168,9 +174,4 @@ class MCPMixin:
 
 
 class HumanoidImMCP(MCPMixin, HumanoidIm):
-
-    def __init__(self, cfg, sim_params=None, physics_engine=None, device_type="cuda", device_id=0, headless=True):
-        self._mcp_config(cfg)
-        super().__init__(cfg=cfg, sim_params=sim_params, physics_engine=physics_engine, device_type=device_type, device_id=device_id,
-                         headless=headless)
-        self._mcp_load()
+    pass

@@ -394,3 +394,29 @@ def make_locomotion_library(model, num_clips=64, seed=0, seconds=8.0, fps=30, wi
     for i in range(n_squat):
         out[f"loco_e_squat_{i:03d}"] = make_gait_clip(model, "squat", seconds, fps, period=float(rng.uniform(2.2, 3.0)), depth=float(rng.uniform(0.12, 0.2)))
     return out
+
+
+def motion_from_spec(spec, model, is_robot=False, default_dof_pos=None, num_extend=0, min_frames=30, base_rot=None):
+    """A `motion_file` value that is a synthetic clip spec -> its motion dict; anything else (a dict, a path, a spec word that is not built for
+    this humanoid family) comes back unchanged.  The word in front of the first `:` decides, as a whole word:
+      stand | armswing [:seconds]                   the rest / default pose standing still, or with swinging arms (robots: shoulder-pitch joints)
+      squat | stepinplace | walk [:seconds]         SMPL family: leg IK on prescribed pelvis / foot trajectories (no sliding; the walk moves at 0.7 m/s)
+      locomotion [:num_clips[:seed[:seconds]]]      SMPL family: a multi-clip set of the feasible clips above
+      synthetic [:num_clips[:seed[:mean_seconds]]]  AMASS-shaped smooth random clips"""
+    kind, *args = spec.split(":") if isinstance(spec, str) else (None,)
+    arg = lambda i, to, default: to(args[i]) if len(args) > i else default
+    if kind == "synthetic" and is_robot:
+        return make_robot_motion_dict(model, arg(0, int, 1), seed=arg(1, int, 0), mean_seconds=arg(2, float, 8.0), num_extend=num_extend, min_frames=min_frames)
+    if kind == "synthetic":
+        return make_motion_dict(model.parent, arg(0, int, 1), seed=arg(1, int, 0), body_names=model.body_names, mean_seconds=arg(2, float, 8.0),
+                                min_frames=min_frames, base_rot=base_rot)
+    if kind in ("stand", "armswing") and is_robot:
+        return {f"{kind}_00000": make_robot_stand_clip(model, default_dof_pos, arg(0, float, 10.0), num_extend=num_extend,
+                                                      arm_swing=0.5 if kind == "armswing" else 0.0)}
+    if kind in ("stand", "armswing") and not is_robot:
+        return {f"{kind}_00000": (make_stand_clip if kind == "stand" else make_armswing_clip)(model, arg(0, float, 10.0))}
+    if kind in ("squat", "stepinplace", "walk") and not is_robot:
+        return {f"{kind}_00000": make_gait_clip(model, kind, arg(0, float, 10.0))}
+    if kind == "locomotion" and not is_robot:
+        return make_locomotion_library(model, arg(0, int, 64), arg(1, int, 0), arg(2, float, 8.0))
+    return spec

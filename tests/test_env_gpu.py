@@ -1406,3 +1406,56 @@ def test_multi_clip_acceptance_pipeline_mechanics(tmp_path):
         assert d["primitive0_frozen_unchanged"] is True and d["stage2_epochs"] > 0
         assert set(d["covered_by_some_primitive"]) == {"rate", "uncovered"}
     assert any("sweep_success_rate" in row for row in d["curve"])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the constructor's host phases (HumanoidIm.host_only) build what the real construction launches with
+# ---------------------------------------------------------------------------------------------------------------
+def _assert_same_value(a, b, where):
+    """numpy / python values, host or device tensors by content, ctypes structs by their bytes, other objects attribute by attribute."""
+    import ctypes
+    if isinstance(a, torch.Tensor):
+        assert isinstance(b, torch.Tensor) and a.dtype == b.dtype and torch.equal(a.cpu(), b.cpu()), where
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and np.array_equal(a, b), where
+    elif isinstance(a, ctypes.Structure):
+        assert type(a) is type(b) and bytes(a) == bytes(b), where
+    elif isinstance(a, dict):
+        assert isinstance(b, dict) and list(a) == list(b), where
+        for k in a:
+            _assert_same_value(a[k], b[k], f"{where}[{k!r}]")
+    elif isinstance(a, (list, tuple)):
+        assert type(a) is type(b) and len(a) == len(b), where
+        for i, (x, y) in enumerate(zip(a, b)):
+            _assert_same_value(x, y, f"{where}[{i}]")
+    elif hasattr(a, "__dict__") and not isinstance(a, type):
+        assert type(a) is type(b), where
+        _assert_same_value(vars(a), vars(b), where)
+    else:
+        assert type(a) is type(b) and a == b, where
+
+
+@pytest.mark.parametrize("over,recovers,num_actions", [
+    ({}, False, 69), (H1_OVER, False, 19),
+    ({"env.task": "HumanoidImGetup", "env.recoveryEpisodeProb": 0.5, "env.recoverySteps": 8, "env.fallInitProb": 0.5}, True, 69),
+    ({"env": "env_im_getup_mcp", "learning": "im_mcp", "env.num_prim": 3}, True, 3)], ids=["smpl", "h1", "getup", "mcp_getup"])
+def test_host_phases_build_what_the_device_phases_launch_with(over, recovers, num_actions):
+    """`host_only` (the constructor's host phases alone) and a real construction from an equal config agree on every attribute the host phases
+    set -- sizes, name lists, index tables, the packed model, phc_sim_params_t -- and the class hooks decide the reset list and the recovery
+    counter; one reset and one step show that the launches accept what the phases built."""
+    from phc_amd.config import compose
+    task, env = make_task(8, **over)
+    ov = ["env.num_envs=8", "env.motion_file=synthetic:3:1"] + [f"{k}={v}" for k, v in over.items()]
+    host = type(task).host_only(compose(ov))
+    assert len(vars(host)) > 100 and "obs_buf" not in vars(host) and "_lib" not in vars(host)
+    for name, value in vars(host).items():
+        _assert_same_value(value, getattr(task, name), name)
+    assert task._use_reset_list is type(task)._use_reset_list is (not recovers)
+    assert (task._reset_list is not None) == task._use_reset_list and (task._recovery_counter is not None) == recovers
+    assert task.num_actions == host.num_actions == num_actions == task.get_action_size()
+    if hasattr(task, "load_primitives"):
+        task.load_primitives(_pnn_checkpoint(task, 3)[0])
+    env.reset()
+    obs, rew, done, info = env.step(torch.zeros(8, num_actions, device=task.device))
+    assert obs.shape == (8, host.num_obs) and info["amp_obs"].shape == (8, host.get_num_amp_obs())
+    assert torch.isfinite(obs).all() and torch.isfinite(rew).all()

@@ -311,36 +311,30 @@ def test_binding_types_the_new_symbol():
     assert len(fn.argtypes) == 12 and fn.restype is _lib.c_i32
 
 
-class _Stub:
-    """The attributes the task-level guards read, without building a task (which needs the GPU)."""
-    def __init__(self, env_shape=None, lane_mapping=0, push=None):
-        from phc_amd import abi
-        self._env_shape, self._push = env_shape, push
-        self._sim_params = abi.sim_params_struct(lane_mapping=lane_mapping)
-        self.num_envs, self.num_bodies, self.device = 2, 4, "cpu"
-        self._ext_force = self._ext_torque = self._ext_pending = None
+def _host_task(*over, push=None):
+    """The task as far as its host phases build it (no device): what the task-level guards read."""
+    from phc_amd.config import compose
+    from phc_amd.env.tasks.humanoid_im import HumanoidIm
+    t = HumanoidIm.host_only(compose(["env.num_envs=2", *over]))
+    t._push, t.device = push, "cpu"     # (the one-shot buffers of the last case below are made on `device`)
+    return t
 
 
 def test_task_level_errors():
-    from phc_amd.env.tasks.humanoid_im import HumanoidIm
     from phc_amd.learning.amp_agent import IMAmpAgent
-
-    class T(_Stub):
-        _check_wrench_supported = HumanoidIm._check_wrench_supported
-        apply_rigid_body_force_tensors = HumanoidIm.apply_rigid_body_force_tensors
-
-    f = torch.zeros(2, 4, 3)
+    T = _host_task
+    f = torch.zeros(2, 24, 3)
     with pytest.raises(NotImplementedError, match="has_shape_variation"):
-        T(env_shape=torch.zeros(2, dtype=torch.int32)).apply_rigid_body_force_tensors(f)
+        T("robot.has_shape_variation=True").apply_rigid_body_force_tensors(f)
     with pytest.raises(NotImplementedError, match="lane_mapping"):
-        T(lane_mapping=3).apply_rigid_body_force_tensors(f)
+        T("+solver.lane_mapping=3").apply_rigid_body_force_tensors(f)
     with pytest.raises(ValueError, match="schedule"):
         T(push=_schedule()).apply_rigid_body_force_tensors(f)
     with pytest.raises(ValueError, match="shape"):
         T().apply_rigid_body_force_tensors(torch.zeros(2, 3, 3))
     t = T()
     t.apply_rigid_body_force_tensors(f + 1.0, None, sim_calls=1)
-    assert t._ext_pending == (True, False, 1) and float(t._ext_force.sum()) == 24.0 and t._ext_torque is None
+    assert t._ext_pending == (True, False, 1) and float(t._ext_force.sum()) == 144.0 and t._ext_torque is None
 
     class A:
         task = T(push=_schedule())
