@@ -78,7 +78,8 @@ typedef struct {
     int32_t dofs_per_joint;           /* 3 spherical (0 is read as 3), 1 revolute */
 } phc_motion_lib_t;
 
-/* Simulator-owned state tensors (S1-S5, S8). */
+/* Simulator-owned state tensors (S1-S5, S8).  Float tensors need 4-byte alignment only; with root_states, dof_state, rigid_body_state, contact_force and
+ * dof_force all 16-byte aligned phc_sim_step takes its staged epilogue (same values, wider stores). */
 typedef struct {
     int32_t num_envs;
     float* root_states;
@@ -331,7 +332,8 @@ int32_t phc_sim_step_wrench(const phc_model_t* model, const phc_sim_params_t* pa
 /* S7 alone: forward kinematics from (root_states, dof_state) to rigid_body_state. */
 int32_t phc_refresh_body_state(const phc_model_t* model, const phc_sim_state_t* sim, void* stream);
 
-/* S7 for a list of envs (after a teleport of root_states / dof_state: gym.set_*_indexed + refresh). */
+/* S7 for a list of envs (after a teleport of root_states / dof_state: gym.set_*_indexed + refresh): rigid_body_state of the `num` listed envs (any order, each
+ * < num_envs), every other row untouched.  num == 0 returns 0 and num < 0 or a null list with num > 0 PHC_EINVAL, all without a launch. */
 int32_t phc_refresh_body_state_indexed(const phc_model_t* model, const phc_sim_state_t* sim, int32_t num, const int64_t* env_ids,
                                        void* stream);
 

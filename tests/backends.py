@@ -53,7 +53,11 @@ class HostEmu:
     def amp_ref_table(self, model, lib, prm, num_frames, next_frame, table):
         return emu().emu_amp_ref_table(P(model), P(lib), P(prm), num_frames, abi.ptr(next_frame), abi.ptr(table))
 
-    def sim_step(self, model, params, sim, actions, off, scale, freeze, num_sim_calls):
+    def sim_step(self, model, params, sim, actions, off, scale, freeze, num_sim_calls, force=None, torque=None, wrench_sim_calls=0):
+        """`force` / `torque` ([N, NB, 3]) given: phc_sim_step_wrench's host statement."""
+        if force is not None or torque is not None:
+            return emu().emu_sim_step_wrench(P(model), P(params), P(sim), abi.ptr(actions), abi.ptr(off), abi.ptr(scale), abi.ptr(freeze), num_sim_calls,
+                                             abi.ptr(force), abi.ptr(torque), wrench_sim_calls)
         return emu().emu_sim_step(P(model), P(params), P(sim), abi.ptr(actions), abi.ptr(off), abi.ptr(scale), abi.ptr(freeze), num_sim_calls, 1)
 
     def refresh_body_state(self, model, sim):
@@ -111,11 +115,19 @@ class Hip:
     def amp_ref_table(self, model, lib, prm, num_frames, next_frame, table):
         return self.lib.phc_amp_ref_table(model, lib, prm, num_frames, abi.ptr(next_frame), abi.ptr(table), self._s())
 
-    def sim_step(self, model, params, sim, actions, off, scale, freeze, num_sim_calls):
+    def sim_step(self, model, params, sim, actions, off, scale, freeze, num_sim_calls, force=None, torque=None, wrench_sim_calls=0):
+        """`force` / `torque` ([N, NB, 3]) given: phc_sim_step_wrench."""
+        if force is not None or torque is not None:
+            return self.lib.phc_sim_step_wrench(model, params, sim, abi.ptr(actions), abi.ptr(off), abi.ptr(scale), abi.ptr(freeze), num_sim_calls,
+                                                abi.ptr(force), abi.ptr(torque), wrench_sim_calls, self._s())
         return self.lib.phc_sim_step(model, params, sim, abi.ptr(actions), abi.ptr(off), abi.ptr(scale), abi.ptr(freeze), num_sim_calls, self._s())
 
     def refresh_body_state(self, model, sim):
         return self.lib.phc_refresh_body_state(model, sim, self._s())
+
+    def refresh_body_state_indexed(self, model, sim, num, env_ids):
+        """(the host emulation has no indexed refresh: device only)"""
+        return self.lib.phc_refresh_body_state_indexed(model, sim, num, abi.ptr(env_ids), self._s())
 
 
 _CACHE = {}
