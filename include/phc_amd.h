@@ -361,6 +361,16 @@ int32_t phc_im_reset(const phc_model_t* model, const phc_motion_lib_t* lib, cons
                      const phc_sim_state_t* sim, const phc_im_buffers_t* buf, int32_t num_reset,
                      const int64_t* env_ids, const float* phase /*[num_reset]*/, int32_t start_at_zero, void* stream);
 
+/* The PLAIN feature set (csrc/phc_im_plain.h; additions to ABI 37, which stays 37): the values the feature selectors of phc_im_params_t / phc_im_buffers_t have in the
+ * default SMPL imitation task.  phc_im_post_physics, phc_im_reset and phc_im_reset_done launch an instantiation of their kernel with those selectors as
+ * compile-time constants when every listed field of the caller's structs has its listed value, the joints are spherical and an env takes 32 lanes -- the same
+ * results bit for bit (no fast-math, no contraction in that translation unit), fewer registers and branches.  Any other task runs the generic kernels as before.
+ * phc_im_is_plain: 1 if the structs satisfy the predicate, else 0 (a null struct: 0).  It looks at the structs only, not at the switch below.
+ * phc_task_force_generic: a process-wide HOST switch; on != 0 sends plain tasks through the generic kernels too (A/B comparisons); returns the previous
+ * value.  A launch captured in a hipGraph holds the kernel chosen at capture. */
+int32_t phc_im_is_plain(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_im_buffers_t* buf);
+int32_t phc_task_force_generic(int32_t on);
+
 /* `reset_done()`: phc_im_reset's masked mode with the start-time phase drawn INSIDE the kernel, so that the rollout idiom
  * "reset the envs that are done" is one launch with no host round trip and no auxiliary torch kernels:
  * phase(env) = 24-bit uniform from a 32-bit avalanche hash of env under the stream key splitmix64(seed, counter) (like

@@ -164,7 +164,13 @@ _SIGNATURES = {
     "phc_eval_accumulate": ([P(MotionLib), P(EvalArgs), c_p], c_i32),
     "phc_push_advance": ([P(PushArgs), c_p], c_i32),
 }
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# Optional symbols: typed when the library has them.  An older build of the same ABI selected with PHC_AMD_LIB (an A/B baseline) lacks them and still loads; a
+# caller that needs one fails on the missing attribute.
+_OPTIONAL_SIGNATURES = {
+    "phc_im_is_plain": ([P(Model), P(MotionLib), P(ImParams), P(ImBuffers)], c_i32),
+    "phc_task_force_generic": ([c_i32], c_i32),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 
 _lib = None
 
@@ -182,6 +188,11 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the .so does not export the symbol
         fn.argtypes = argtypes
         fn.restype = restype
+    for name, (argtypes, restype) in _OPTIONAL_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = argtypes
+            fn.restype = restype
     if lib.phc_abi_version() != 37:
         raise ImportError("libphc_amd.so ABI version mismatch")
     _lib = lib

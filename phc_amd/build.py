@@ -11,6 +11,7 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #   task kernels: parity with the reference's torch ops is pinned at 1e-5 and torch does not fuse multiply-add, so
 #     -ffp-contract=off (e.g. sqrt(1 - w*w) in quat_to_angle_axis is cancellation-prone: a contracted fma moves exp-map
 #     outputs by 1e-3); -fno-slp-vectorize avoids v_pk_* register marshalling (reset 68 -> 49 us, post-physics 35 -> 27 us).
+#     phc_kernels_plain.hip holds the plain instantiations of the two env-step task kernels (phc_task_kernel.h) and is compiled with the same flags.
 #   stepper: see the header of phc_sim.hip (-ffast-math -fno-slp-vectorize: 158 -> 109 us).  phc_sim_wrench.hip holds the external-wrench instantiations of the
 #     same kernel (phc_sim_kernel.h) and is compiled with the same flags.
 #   learner kernels: bandwidth-bound passes; IEEE division / no contraction so the normalised values equal torch's.
@@ -18,11 +19,11 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #   renderer (phc_render.hip, off the training path): IEEE fp32 (no fast-math): its error bound assumes correctly rounded sqrt / division.
 #   evaluation metrics (phc_eval.hip): no contraction -- its reference positions are bit-equal to phc_motion_state's.
 #   push schedule (phc_push.hip): no contraction, no fast-math -- its integer state is bit-equal to the host build of phc_push.h.
-SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
+SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_kernels_plain.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
            "phc_push.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", os.path.join("..", "..", "include", "phc_amd.h")]
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

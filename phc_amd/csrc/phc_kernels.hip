@@ -10,53 +10,12 @@
 #include <type_traits>
 #include "phc_im.h"
 #include "phc_im_check.h"  // what the entry points refuse
-#include "phc_group.h"  // group_sum / group_or
+#include "phc_task_kernel.h"  // k_im_post_physics, k_im_reset; im_is_plain
 
 using namespace phc;
 
-// ------------------------------------------------------------------------------------------
-// post_physics_step of the imitation task.  blockDim = 256 (8 envs).
-// ------------------------------------------------------------------------------------------
-// The task kernels are instantiated per joint family (DPJ = DoFs per joint: 3 spherical / 1 revolute) with the struct fields
-// that select the family pinned to compile-time constants, so the SMPL instantiation carries none of the robot branches.
-template <int DPJ>
-__device__ __forceinline__ void pin_family(phc_motion_lib_t& lib, phc_im_params_t& prm) {
-    lib.dofs_per_joint = DPJ; prm.dofs_per_joint = DPJ;
-    if (DPJ == 3) { lib.num_ext_bodies = 0; prm.num_ext_bodies = 0; }
-}
-
-template <int DPJ, int G>
-__global__ __launch_bounds__(256) void k_im_post_physics(phc_model_t model, phc_motion_lib_t lib, phc_im_params_t prm,
-                                                        phc_sim_state_t sim, phc_im_buffers_t buf, int n_reset_bodies) {
-    pin_family<DPJ>(lib, prm);
-    const int lane = threadIdx.x & (G - 1);
-    const int64_t env = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    if (env >= sim.num_envs) return;  // whole lane group exits together
-    PHC_PTL(0, env, lane)
-    if (blockIdx.x == 0 && threadIdx.x == 0 && buf.reset_rng_counter) *buf.reset_rng_counter += 1;   // (one writer; no reset launch runs concurrently)
-    // Everything the launch reads that does not depend on something else it reads is REQUESTED here, before the first wait: the clip's table
-    // entries, the body's and the root's state, the per-env scalars of the prologue (a wavefront waits for a load at its first use; this
-    // kernel's wavefronts spend three quarters of their life waiting, profiles/r03_task/post_physics_timeline.txt)
-    const int64_t progress = buf.progress_buf[env] + 1;  // humanoid.py:1637
-    const FrameTab tab = frame_tab(lib, motion_id_of(buf, env));
-    const int jb = lane < model.num_bodies ? lane : 0;
-    const BodyState body = load_body(sim.rigid_body_state, env, model.num_bodies, jb);
-    const BodyState root = load_body(sim.rigid_body_state, env, model.num_bodies, 0);
-    const ImStepCtx c = im_post_prologue(lib, prm, sim, buf, env, progress);
-    const float prev_goal = (prm.zero_out_far && buf.point_goal) ? buf.point_goal[env] : 0.f;  // read before lane 0 overwrites it
-    PHC_PTL(1, env, lane)
-    RewardPartial rp = im_post_lane(model, lib, prm, sim, buf, env, lane, c, tab, body, root);
-    PHC_PTL(9, env, lane)
-    amp_shift_lane(prm, buf, env, lane, G);   // (every S-th step; reads the old window, writes rows 1.. of the new one: after the frame in row 0)
-    float s_pos = group_sum<G>(rp.pos), s_rot = group_sum<G>(rp.rot), s_vel = group_sum<G>(rp.vel), s_ang = group_sum<G>(rp.angvel);
-    float s_pow = group_sum<G>(rp.power), s_dist = group_sum<G>(rp.dist);
-    int fallen = group_or<G>(rp.fallen);
-    PHC_PTL(10, env, lane)
-    if (lane == 0)
-        im_post_finalize(lib, prm, buf, model.num_bodies, env, c, progress, s_pos, s_rot, s_vel, s_ang, s_pow, s_dist, rp.root_dist,
-                         prev_goal, fallen, n_reset_bodies);
-    PHC_PTL(11, env, lane)
-}
+// The two task kernels of the env step, k_im_post_physics and k_im_reset, are templates in phc_task_kernel.h; this file instantiates the generic ones (through
+// task_launch below), phc_kernels_plain.hip the plain ones.
 #ifdef PHC_SIM_PROFILE
 extern "C" int32_t phc_debug_post_timeline(unsigned long long* out32, long long env) {
     if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(phc::g_phc_ptl), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
@@ -90,54 +49,14 @@ __global__ __launch_bounds__(256) void k_im_reset_from_state(phc_model_t model, 
     im_reset_from_state_lane(model, lib, prm, sim, buf, env_ids[r], lane, fill_history);
 }
 
-// Reset of a list of envs.  One lane group per (env, AMP history frame k): group k == 0 also imposes the state
-// and recomputes the observations.  blockDim = 256.
-// (which env and which start time: im_reset_pick, phc_im.h)
-
 #ifdef PHC_SIM_PROFILE   // one lane group's timeline through the reset kernel (scripts/probes/reset_timeline.py; the product library has none of this)
-__device__ unsigned long long g_phc_rtl[64];
-__device__ int g_phc_rtl_group = -1;   // r * 16 + k of the group that stamps
 extern "C" int32_t phc_debug_reset_timeline(unsigned long long* out64, int32_t group) {
     if (out64 && hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_phc_rtl), sizeof(g_phc_rtl)) != hipSuccess) return -1;
     unsigned long long z[64] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_phc_rtl), z, sizeof(z)) != hipSuccess) return -1;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_phc_rtl_group), &group, sizeof(group)) == hipSuccess ? 0 : -1;
 }
-#define PHC_RTL(i) if (rtl_on) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = __builtin_readcyclecounter(); \
-        if (lane == 0) g_phc_rtl[i] = t_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define PHC_RTL(i)
 #endif
-
-// Measured alternative (round 2, profiles/r02_notes.md): ONE workgroup per listed env with its S history-frame groups side by side
-// (blockDim = G * S), so that the S lookups of an env -- S + 1 consecutive clip frames -- share a CU's L1: 46.6 us vs 34 us for this
-// geometry (the ten groups of an env then hit one clip region, i.e. the same HBM channels, at the same instant).  Not kept.
-template <int DPJ, bool RNG, int G>
-__global__ __launch_bounds__(256) void k_im_reset(phc_model_t model, phc_motion_lib_t lib, phc_im_params_t prm, phc_sim_state_t sim,
-                                                 phc_im_buffers_t buf, int num_reset, const int64_t* __restrict__ env_ids,
-                                                 const float* __restrict__ phase, int start_at_zero, uint64_t rng_key) {
-    pin_family<DPJ>(lib, prm);
-    const int lane = threadIdx.x & (G - 1);
-    // listed env (grid.x); grid.y: 0 = state + self observation, 1 = task observation, 2 + k = AMP history frame k -- the heaviest groups
-    // are dispatched first and no group carries more than one lookup chain
-    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const int k = (int)blockIdx.y;
-#ifdef PHC_SIM_PROFILE
-    const bool rtl_on = (int)(r * 16 + k) == g_phc_rtl_group;
-#endif
-    PHC_RTL(0)
-    if (!im_reset_pick_live<RNG>(buf, r, k, lane, num_reset, env_ids)) return;
-    const int64_t env = im_reset_pick_env<RNG>(buf, r, env_ids);
-    const float t = im_reset_pick_time<RNG>(buf, lib, env, r, phase, start_at_zero, rng_key);   // (PHC_RTL(1) stood inside the pick)
-    PHC_RTL(2)
-    if (k < 2) im_reset_lane(model, lib, prm, sim, buf, env, lane, t, env_ids != nullptr, 1 << k);
-    PHC_RTL(3)
-    if (k >= 2) {
-        if (prm.amp_ref_table != nullptr) im_reset_amp_table_lane(lib, prm, buf, model.num_bodies, env, lane, G, t, k - 2);
-        else im_reset_amp_lane(lib, prm, buf, model.num_bodies, env, lane, t, k - 2);
-    }
-    PHC_RTL(4)
-}
 
 // build_amp_obs_demo: n samples x S history steps.  One lane group per (sample, step).
 template <int G>
@@ -227,25 +146,45 @@ static inline int32_t launch_status() {
     return e == hipSuccess ? 0 : (int32_t)e;
 }
 static inline int env_blocks(int64_t groups, int lanes) { return (int)((groups * lanes + 255) / 256); }
-// lanes per env: 32 while the articulation (with its extended reference bodies) fits, else 64
-static inline int group_lanes(int num_bodies, int num_ext) { return num_bodies + num_ext > 32 ? 64 : 32; }
+// (lanes per env: group_lanes, phc_im_plain.h)
 
-// The launch chooser of the task kernels: the run-time pair (joint family, lanes per env) as compile-time constants.  `launch(dpj, g)` is a generic lambda that
-// names its kernel with them -- k<dpj, g>, or k<g> for the kernels the family does not specialise -- and launches it.
+// The launch chooser of the task kernels: the run-time triple (joint family, lanes per env, plain feature set) as compile-time constants.  `launch(dpj, g, plain)`
+// is a generic lambda that names its kernel with them -- k<dpj, g, plain>, k<dpj, g> or k<g> for the kernels that do not specialise further -- and launches it.
+// `plain` (im_is_plain, phc_im_plain.h) implies the spherical family at 32 lanes: the one shape the plain kernels are instantiated for.
 template <int V> using int_c = std::integral_constant<int, V>;
 template <class F>
-static inline int32_t task_launch(bool revolute, int lanes, F launch) {
-    if (revolute) { if (lanes == 64) launch(int_c<1>(), int_c<64>()); else launch(int_c<1>(), int_c<32>()); }
-    else { if (lanes == 64) launch(int_c<3>(), int_c<64>()); else launch(int_c<3>(), int_c<32>()); }
+static inline int32_t task_launch(bool revolute, int lanes, bool plain, F launch) {
+    constexpr std::false_type no;
+    if (plain) launch(int_c<3>(), int_c<32>(), std::true_type());
+    else if (revolute) { if (lanes == 64) launch(int_c<1>(), int_c<64>(), no); else launch(int_c<1>(), int_c<32>(), no); }
+    else { if (lanes == 64) launch(int_c<3>(), int_c<64>(), no); else launch(int_c<3>(), int_c<32>(), no); }
     return launch_status();
+}
+
+// the plain instantiations live in phc_kernels_plain.hip
+extern template __global__ void k_im_post_physics<3, 32, true>(phc_model_t, phc_motion_lib_t, phc_im_params_t, phc_sim_state_t, phc_im_buffers_t, int);
+extern template __global__ void k_im_reset<3, false, 32, true>(phc_model_t, phc_motion_lib_t, phc_im_params_t, phc_sim_state_t, phc_im_buffers_t, int, const int64_t* __restrict__,
+                                                               const float* __restrict__, int, uint64_t);
+extern template __global__ void k_im_reset<3, true, 32, true>(phc_model_t, phc_motion_lib_t, phc_im_params_t, phc_sim_state_t, phc_im_buffers_t, int, const int64_t* __restrict__,
+                                                              const float* __restrict__, int, uint64_t);
+
+// phc_task_force_generic: a process-wide host switch that sends plain tasks through the generic kernels too (the A/B of tests/test_task_plain_gpu.py and of
+// profiles/task_plain_instantiation).  The instrumented library stamps the generic kernels only.
+#ifdef PHC_SIM_PROFILE
+static int32_t g_force_generic = 1;
+#else
+static int32_t g_force_generic = 0;
+#endif
+static inline bool launch_plain(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_im_buffers_t* buf) {
+    return !g_force_generic && im_is_plain(model, lib, prm, buf);
 }
 
 // both reset launches: `n` lane groups per row of the grid
 template <bool RNG>
 static int32_t reset_launch(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
                             const phc_im_buffers_t* buf, int n, const int64_t* env_ids, const float* phase, int start_at_zero, uint64_t key, void* stream) {
-    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto dpj, auto g) {
-        hipLaunchKernelGGL((k_im_reset<dpj(), RNG, g()>), dim3(env_blocks(n, g()), prm->num_amp_obs_steps + 2), dim3(256), 0, (hipStream_t)stream, *model, *lib,
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), launch_plain(model, lib, prm, buf), [&](auto dpj, auto g, auto plain) {
+        hipLaunchKernelGGL((k_im_reset<dpj(), RNG, g(), plain()>), dim3(env_blocks(n, g()), prm->num_amp_obs_steps + 2), dim3(256), 0, (hipStream_t)stream, *model, *lib,
                            *prm, *sim, *buf, n, env_ids, phase, start_at_zero, key);
     });
 }
@@ -254,12 +193,22 @@ extern "C" {
 
 int32_t phc_abi_version(void) { return PHC_ABI_VERSION; }
 
+int32_t phc_task_force_generic(int32_t on) {
+    const int32_t old = g_force_generic;
+    g_force_generic = on ? 1 : 0;
+    return old;
+}
+
+int32_t phc_im_is_plain(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_im_buffers_t* buf) {
+    return im_is_plain(model, lib, prm, buf) ? 1 : 0;
+}
+
 int32_t phc_motion_state(const phc_motion_lib_t* lib, int32_t n, const int64_t* motion_ids, const float* motion_times,
                          const float* offset, float* rg_pos, float* rb_rot, float* body_vel, float* body_ang_vel,
                          float* dof_pos, float* dof_vel, int64_t* frame_idx0, int64_t* frame_idx1, float* blend, float* rg_pos_ext,
                          float* rb_rot_ext, void* stream) {
     if (int32_t rc = check_motion_state(lib, n); rc || n == 0) return rc;
-    return task_launch(lib->dofs_per_joint == 1, group_lanes(lib->num_bodies, lib->num_ext_bodies), [&](auto, auto g) {
+    return task_launch(lib->dofs_per_joint == 1, group_lanes(lib->num_bodies, lib->num_ext_bodies), false, [&](auto, auto g, auto) {
         hipLaunchKernelGGL(k_motion_state<g()>, dim3(env_blocks(n, g())), dim3(256), 0, (hipStream_t)stream, *lib, n, motion_ids, motion_times, offset,
                            rg_pos, rb_rot, body_vel, body_ang_vel, dof_pos, dof_vel, frame_idx0, frame_idx1, blend, rg_pos_ext, rb_rot_ext);
     });
@@ -277,8 +226,8 @@ int32_t phc_im_post_physics(const phc_model_t* model, const phc_motion_lib_t* li
                             const phc_sim_state_t* sim, const phc_im_buffers_t* buf, void* stream) {
     if (int32_t rc = check_im_post_physics(model, lib, prm, sim, buf); rc || sim->num_envs == 0) return rc;
     const int n_reset_bodies = prm->num_reset_bodies > 0 ? prm->num_reset_bodies : 1;
-    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto dpj, auto g) {
-        hipLaunchKernelGGL((k_im_post_physics<dpj(), g()>), dim3(env_blocks(sim->num_envs, g())), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim,
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), launch_plain(model, lib, prm, buf), [&](auto dpj, auto g, auto plain) {
+        hipLaunchKernelGGL((k_im_post_physics<dpj(), g(), plain()>), dim3(env_blocks(sim->num_envs, g())), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim,
                            *buf, n_reset_bodies);
     });
 }
@@ -289,7 +238,7 @@ int32_t phc_amp_ref_table(const phc_model_t* model, const phc_motion_lib_t* lib,
     const int lanes = group_lanes(model->num_bodies, prm->num_ext_bodies);
     const int64_t blocks = (num_frames * lanes + 255) / 256;
     if (blocks > 0x7fffffffLL) return PHC_EUNSUPPORTED;   // (launch geometry, not an argument check: grid.x is 31 bits)
-    return task_launch(prm->dofs_per_joint == 1, lanes, [&](auto dpj, auto g) {
+    return task_launch(prm->dofs_per_joint == 1, lanes, false, [&](auto dpj, auto g, auto) {
         hipLaunchKernelGGL((k_amp_ref_table<dpj(), g()>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, num_frames, next_frame,
                            table);
     });
@@ -313,7 +262,7 @@ int32_t phc_im_reset_from_state(const phc_model_t* model, const phc_motion_lib_t
                                 const phc_sim_state_t* sim, const phc_im_buffers_t* buf, int32_t num_reset, const int64_t* env_ids,
                                 int32_t fill_history, void* stream) {
     if (int32_t rc = check_im_reset_from_state(model, lib, prm, sim, buf, num_reset, env_ids); rc || num_reset == 0) return rc;
-    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto, auto g) {
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), false, [&](auto, auto g, auto) {
         hipLaunchKernelGGL(k_im_reset_from_state<g()>, dim3(env_blocks(num_reset, g())), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim, *buf,
                            num_reset, env_ids, fill_history);
     });
@@ -322,7 +271,7 @@ int32_t phc_im_reset_from_state(const phc_model_t* model, const phc_motion_lib_t
 int32_t phc_amp_obs_demo(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, int32_t n,
                          const int64_t* motion_ids, const float* motion_times0, float* amp_obs_demo, void* stream) {
     if (int32_t rc = check_amp_obs_demo(model, lib, prm, n); rc || n == 0) return rc;
-    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), [&](auto, auto g) {
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), false, [&](auto, auto g, auto) {
         hipLaunchKernelGGL(k_amp_obs_demo<g()>, dim3(env_blocks(n, g()), prm->num_amp_obs_steps), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, n,
                            motion_ids, motion_times0, amp_obs_demo);
     });

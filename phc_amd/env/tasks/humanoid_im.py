@@ -620,6 +620,13 @@ class HumanoidIm:
         b.reset_list = abi.ptr(self._reset_list)     # (callers clear it for the masked sweep: restored on every use)
         return b
 
+    def is_plain(self):
+        """Do this task's structs have the plain feature set (csrc/phc_im_plain.h), i.e. do its post-physics and reset launches take the kernels compiled for
+        it?  Decided per launch by the library from `_im_params` and the buffers struct: both are covered by `launch_generation()` (the parameter struct's
+        generation and the clip-id table mode; the nullable buffers are fixed at construction), so a captured launch is re-chosen whenever the answer can change."""
+        buf = self._buffers(self._amp_window(self._amp_head), self._amp_window(self._next_amp_head()))
+        return bool(self._lib.phc_im_is_plain(self._model_struct, self._motion_lib.struct, self._im_params, buf))
+
     def _buffer_tensors(self):
         """Every tensor whose address `_buffers_uncached` stores (the AMP windows are views of `_amp_strip`)."""
         return (self.progress_buf, self.reset_buf, self._terminate_buf, self.rew_buf, self.reward_raw, self.obs_buf, self._sampled_motion_ids,
