@@ -55,7 +55,11 @@ typedef struct {
     int32_t max_body_contact_pts; /* ABI 36: the largest number of ground-contact points any one body carries (int table 9; the maximum over the shapes).  The per-point
                                    * masks of the solver are finite: phc_sim_step returns PHC_EUNSUPPORTED for contact_model 1 above 32 (c_active / c_removed) and for
                                    * inertia_lag above 64 (c_touch: the tail points of a lagged sub-step would lose their force while their impedance stays in I^A) */
+    int32_t sim_plain_facts;      /* what phc_sim_model_facts returned for the HOST copy of these tables (PHC_SIM_FACTS_PLAIN), or 0 = not examined: the stepper's launch
+                                   * chooser cannot read the device tables, so the model facts of csrc/phc_sim_plain.h travel with the struct.  The field takes what was
+                                   * the struct's tail padding: size and layout of ABI 37 are unchanged, and a caller that zero-fills the struct gets the generic kernels */
 } phc_model_t;
+#define PHC_SIM_FACTS_PLAIN 0x504c4e01
 
 /* Flat reference-motion buffer.  Replaces MotionLibBase's gts/grs/lrs/gvs/gavs/dvs tensors
  * (phc/utils/motion_lib_base.py:300-318; H1/G1: motion_lib_real.py:196-215).  One record per frame, fields contiguous:
@@ -328,6 +332,21 @@ int32_t phc_sim_step_wrench(const phc_model_t* model, const phc_sim_params_t* pa
                             const float* actions /*[N,D]*/, const float* pd_action_offset /*[D]*/, const float* pd_action_scale /*[D]*/,
                             const int32_t* freeze_mask /*[D]*/, int32_t num_sim_calls,
                             const float* ext_force /*[N,NB,3]*/, const float* ext_torque /*[N,NB,3]*/, int32_t wrench_sim_calls, void* stream);
+
+/* The PLAIN launch of the stepper (csrc/phc_sim_plain.h; additions to ABI 37, which stays 37): phc_sim_step launches an instantiation of its kernel with the launch
+ * options, the nullable pointers and the tree constants of the default SMPL task as compile-time constants when every entry of that list holds for the caller's
+ * structs and arguments.  That kernel also forms what is fixed for a launch -- the implicit drive diagonals -- once instead of in every sub-step.  The translation unit is compiled with fast-math like the generic one: results agree within the stepper's tolerance against its double-precision
+ * recursion, not bit for bit.  Every other launch (and phc_sim_step_wrench with a wrench) runs the generic kernels as before.
+ * phc_sim_model_facts: `model` with ints / floats at HOST addresses -> PHC_SIM_FACTS_PLAIN if the tables satisfy the model facts of the list (counts, solver tree,
+ *   one shape block, <= 32 contact points per body, every joint with equal per-axis kp, kd and armature), else 0.  The caller stores it in phc_model_t.sim_plain_facts
+ *   of the struct it launches with (phc_amd/abi.py model_struct does).
+ * phc_sim_is_plain: 1 if structs and arguments satisfy the predicate, else 0 (a null struct: 0).  It does not look at the switch below.
+ * phc_sim_force_generic: a process-wide HOST switch; on != 0 sends plain launches through the generic kernel too (A/B comparisons); returns the previous value.
+ *   The instrumented build (-DPHC_SIM_PROFILE) starts with it on.  A launch captured in a hipGraph holds the kernel chosen at capture. */
+int32_t phc_sim_model_facts(const phc_model_t* model_on_host);
+int32_t phc_sim_is_plain(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim, const float* actions,
+                         const int32_t* freeze_mask, int32_t num_sim_calls);
+int32_t phc_sim_force_generic(int32_t on);
 
 /* S7 alone: forward kinematics from (root_states, dof_state) to rigid_body_state. */
 int32_t phc_refresh_body_state(const phc_model_t* model, const phc_sim_state_t* sim, void* stream);

@@ -24,7 +24,7 @@ c_p = C.c_void_p
 class Model(C.Structure):
     _fields_ = [("num_bodies", c_i32), ("num_dof", c_i32), ("max_level", c_i32), ("num_contact_pts", c_i32),
                 ("ints", c_p), ("floats", c_p), ("num_collision_pairs", c_i32),
-                ("num_shapes", c_i32), ("int_stride", c_i32), ("float_stride", c_i32), ("max_body_contact_pts", c_i32)]
+                ("num_shapes", c_i32), ("int_stride", c_i32), ("float_stride", c_i32), ("max_body_contact_pts", c_i32), ("sim_plain_facts", c_i32)]
 
 
 class MotionLib(C.Structure):
@@ -169,6 +169,9 @@ _SIGNATURES = {
 _OPTIONAL_SIGNATURES = {
     "phc_im_is_plain": ([P(Model), P(MotionLib), P(ImParams), P(ImBuffers)], c_i32),
     "phc_task_force_generic": ([c_i32], c_i32),
+    "phc_sim_model_facts": ([P(Model)], c_i32),
+    "phc_sim_is_plain": ([P(Model), P(SimParams), P(SimState), c_p, c_p, c_i32], c_i32),
+    "phc_sim_force_generic": ([c_i32], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

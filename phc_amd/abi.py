@@ -38,7 +38,23 @@ def model_struct(ints, floats, num_bodies, num_dof, max_level, num_contact_pts, 
     per_body = ints.reshape(max(1, int(num_shapes)), -1)[:, 4 + 9 * MAX_BODIES:4 + 10 * MAX_BODIES]   # int table 9: contact points per body
     m.max_body_contact_pts = int(per_body.max())
     m.ints, m.floats = ptr(ints), ptr(floats)
+    m.sim_plain_facts = _sim_plain_facts(m, ints, floats)
     return m
+
+
+def _sim_plain_facts(m, ints, floats):
+    """phc_model_t.sim_plain_facts: what phc_sim_model_facts says about a HOST copy of the tables (the stepper's launch chooser cannot read device memory;
+    csrc/phc_sim_plain.h).  0 -- the generic kernels -- for stacked shape blocks and for a library that predates the function (an A/B baseline)."""
+    fn = getattr(L.load(), "phc_sim_model_facts", None)
+    if fn is None or m.num_shapes > 1:
+        return 0
+    hi, hf = (np.ascontiguousarray(t if isinstance(t, np.ndarray) else t.detach().cpu().numpy()) for t in (ints, floats))
+    if hi.dtype != np.int32 or hf.dtype != np.float32:   # (the double-precision host emulation packs float64 tables)
+        return 0
+    h = L.Model()
+    C.memmove(C.byref(h), C.byref(m), C.sizeof(m))
+    h.ints, h.floats = hi.ctypes.data, hf.ctypes.data
+    return int(fn(C.byref(h)))
 
 
 def motion_lib_struct(frames, frame_stride, num_bodies, motion_lengths, motion_dt, motion_num_frames, length_starts,

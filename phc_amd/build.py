@@ -13,17 +13,17 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #     outputs by 1e-3); -fno-slp-vectorize avoids v_pk_* register marshalling (reset 68 -> 49 us, post-physics 35 -> 27 us).
 #     phc_kernels_plain.hip holds the plain instantiations of the two env-step task kernels (phc_task_kernel.h) and is compiled with the same flags.
 #   stepper: see the header of phc_sim.hip (-ffast-math -fno-slp-vectorize: 158 -> 109 us).  phc_sim_wrench.hip holds the external-wrench instantiations of the
-#     same kernel (phc_sim_kernel.h) and is compiled with the same flags.
+#     same kernel (phc_sim_kernel.h) and is compiled with the same flags; so is phc_sim_plain.hip, the plain instantiation of the default SMPL task's launch (phc_sim_plain.h).
 #   learner kernels: bandwidth-bound passes; IEEE division / no contraction so the normalised values equal torch's.
 #   matrix-core kernels (phc_gemm.hip): no contraction either (the fp32 slab and bias sums are plain adds in a fixed order).
 #   renderer (phc_render.hip, off the training path): IEEE fp32 (no fast-math): its error bound assumes correctly rounded sqrt / division.
 #   evaluation metrics (phc_eval.hip): no contraction -- its reference positions are bit-equal to phc_motion_state's.
 #   push schedule (phc_push.hip): no contraction, no fast-math -- its integer state is bit-equal to the host build of phc_push.h.
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_kernels_plain.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
-           "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"],
+           "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_sim_plain.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
            "phc_push.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", os.path.join("..", "..", "include", "phc_amd.h")]
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

@@ -509,10 +509,27 @@ PHC_HD void aba_add_wrench(AbaLane& L, V3 mc, float mass, V3 F, V3 T) {
 // state, the explicit part F0 of the contact law for the points whose impedance the kept I^A holds (L.c_touch), body-body forces, drive torque.
 // `ext_on`, `ext_f`, `ext_t`: the body's external wrench of this sub-step (aba_add_wrench; phc_sim_step_wrench only).  Applied with the bias force, in every pass and
 // every lagged sub-step (p^A starts afresh there): R m (com - off) is at hand at that point, and behind the contact points it would have to be kept or formed again.
-template <int JT, bool RIGID>
+// `PL` / `pd` (the plain stepper launch only, phc_sim_plain.h; 0 / nullptr everywhere else, the host emulation included): what that launch knows at compile time
+// or formed once before its sub-step loop --
+//   ABA_PL_NO_CP_TAIL    no body has more contact points than the mask has bits: no tail loop behind the set-bit walk;
+//   ABA_PL_DRIVE_CONST   spherical joints with equal per-axis gains: kp, kd + dt kp and the effort limits come from `pd`; L.dimp and L.diso were set before the
+//                        loop (aba_plain_drive) and stand, L.Dw is never formed.
+// (The target quaternion and LDS copies of the per-body constants were built the same way, measured and taken out: profiles/stepper_plain_instantiation/README.md.)
+#define ABA_PL_NO_CP_TAIL 1
+#define ABA_PL_DRIVE_CONST 2
+struct AbaPlainDrive { float kp, kdp; V3 eff; };
+// the launch-invariant drive terms of body j's own joint (level > 0, equal per-axis gains): `pd`, L.dimp = dt kd + dt^2 kp, L.diso = L.dimp + armature
+PHC_HD void aba_plain_drive(AbaLane& L, AbaPlainDrive& pd, const float* f, float dt) {
+    const float kp = f[13], kd = f[16];
+    pd.kp = kp; pd.kdp = kd + dt * kp; pd.eff = v3(f[22], f[23], f[24]);
+    const float d = dt * kd + dt * dt * kp;
+    L.dimp = v3(d, d, d);
+    L.diso = d + f[19];
+}
+template <int JT, bool RIGID, int PL = 0>
 PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params_t& prm, float dt, int j, bool new_sim_call,
                           const float* f, int cp_start, int cp_total, bool reroot, int pass, bool lag = false,
-                          bool ext_on = false, V3 ext_f = V3(), V3 ext_t = V3()) {
+                          bool ext_on = false, V3 ext_f = V3(), V3 ext_t = V3(), const AbaPlainDrive* pd = nullptr) {
     constexpr bool BATCH = aba_batched_constants<JT, RIGID>();
     const float mass = BATCH ? L.mass : f[3];
     // every spatial quantity of the body is taken about its solver reference point o = p + R off (the origin unless the body is reversed)
@@ -520,7 +537,7 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
     // (BATCH: the gains, effort limits and armature the drive at the end of this function needs are requested here, with the inertia: they arrive while the
     //  contact points are worked on instead of costing a round trip of their own behind them)
     float fd[12];
-    if (BATCH) for (int k = 0; k < 12; ++k) fd[k] = f[13 + k];
+    if (BATCH && !(PL & ABA_PL_DRIVE_CONST)) for (int k = 0; k < 12; ++k) fd[k] = f[13 + k];
     M3 R = quat_to_mat(L.Q);
     // ground contact, penalty model, part 1: which points touch.  BATCH: ahead of the inertia, so that the point loads are in flight together with the
     // constants above; otherwise where it always was, behind the inertia.
@@ -599,6 +616,7 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
         }
     }
     if (!lag) {
+        if (!(PL & ABA_PL_NO_CP_TAIL))
         for (int k = PHC_CP_BITS; k < cp_count; ++k) cp_point(cp_load(k));   // (bodies with more points than the mask has bits: the rest one by one; a lagged sub-step leaves them out)
         L.c_touch = pushed;
     }
@@ -665,6 +683,15 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
     if (L.level > 0) {
         Q4 qt = quat_from_rotvec(L.target);
         V3 err = quat_to_rotvec(quat_mul16(quat_conjugate(L.q), qt));
+        if (PL & ABA_PL_DRIVE_CONST) {   // (equal per-axis gains; L.dimp / L.diso stand)
+            const float kp = pd->kp, kdp = pd->kdp;
+            const V3 eff = pd->eff;
+            const V3 tau = v3(fminf(fmaxf(kp * err.x, -eff.x), eff.x) - kdp * L.wj.x, fminf(fmaxf(kp * err.y, -eff.y), eff.y) - kdp * L.wj.y,
+                              fminf(fmaxf(kp * err.z, -eff.z), eff.z) - kdp * L.wj.z);
+            L.tau_local = tau;
+            L.tau_w = mat_mul(R, tau);
+            return;
+        }
         // effort limit (gear=500): the SPRING term saturates; the damping term stays fully implicit, so a saturated
         // drive can never inject energy (a hard clamp of the total would turn the drive into a constant torque on a
         // 0.02 kg m^2 armature -> 1e4 rad/s^2)
@@ -957,7 +984,9 @@ PHC_HD void accumulate_child(Inertia6& I, Force6& p, const float* s, int es) {
 //     p^a = p^A + I^a c + U D^-1 u = p^A + I^A c + U D^-1 (u - U^T c),      U^T c = A c_w + B c_a = (I^A c)_top,
 // i.e. two 3x3 products with c, one with D^-1 and two with its result: ~75 multiply-adds and a 6-float hand-over instead of the ~350 and 27 floats of
 // the full step -- no 3x3 inverse, no projected inertia, no congruence.
-template <int JT>
+// `ISO` (the plain stepper launch, phc_sim_plain.h): every joint's drive diagonal is known to be a multiple of the identity (L.diso >= 0), so neither the test
+// nor the general 3x3 form is compiled in.
+template <int JT, bool ISO = false>
 PHC_HD void aba_backward_level(AbaLane& L, int level, int j, const Xch& x, bool lag = false) {
     if (L.slevel != level) return;
     if (lag) {
@@ -999,7 +1028,7 @@ PHC_HD void aba_backward_level(AbaLane& L, int level, int j, const Xch& x, bool 
         const float ids = 1.0f / (dot(a, sym_mul(L.IA.A, a)) + L.dimp.x + L.arm.x);
         L.Di.xx = a.x * a.x * ids; L.Di.xy = a.x * a.y * ids; L.Di.xz = a.x * a.z * ids;
         L.Di.yy = a.y * a.y * ids; L.Di.yz = a.y * a.z * ids; L.Di.zz = a.z * a.z * ids;
-    } else if (L.diso < 0.f) {
+    } else if (!ISO && L.diso < 0.f) {
         Sym3 D = L.Dw;
         D.xx += L.IA.A.xx; D.xy += L.IA.A.xy; D.xz += L.IA.A.xz; D.yy += L.IA.A.yy; D.yz += L.IA.A.yz; D.zz += L.IA.A.zz;
         L.Di = sym_inv(D);
@@ -1010,7 +1039,7 @@ PHC_HD void aba_backward_level(AbaLane& L, int level, int j, const Xch& x, bool 
     V3 a0 = v3(A.xx, A.xy, A.xz), a1 = v3(A.xy, A.yy, A.yz), a2 = v3(A.xz, A.yz, A.zz);  // columns (=rows) of A
     V3 bc0 = v3(B[0], B[3], B[6]), bc1 = v3(B[1], B[4], B[7]), bc2 = v3(B[2], B[5], B[8]);  // columns of B
     Inertia6 Ia;
-    if (JT != PHC_JT_REVOLUTE && L.diso >= 0.f) {
+    if (JT != PHC_JT_REVOLUTE && (ISO || L.diso >= 0.f)) {
         // D = A + d 1 with a scalar d: A = D - d 1, so A P = 1 - d P (P = D^-1) and
         //   A_a = A - A P A = d (A P) (symmetric) ;  B_a = B - A P B = d P B ;  C_a = C - B^T P B
         // -- 39 multiply-adds fewer per level-step than the general expressions below
@@ -1097,22 +1126,31 @@ PHC_HD void aba_accel_level(AbaLane& L, int level, int j, const Xch& x) {
 // Before the backward sweep: a reversed body's solver joint is its solver parent's joint.  Every body publishes the world-frame drive
 // terms of its OWN joint (slot [19..28): tau_w, D_w); a reversed body then takes its solver parent's -- the torque with the opposite
 // sign, the joint-space matrix as it is (same physical joint, seen from its other side).
-PHC_HD void aba_publish_drive(const AbaLane& L, int j, const Xch& x) {
+// `tau_only` (the plain stepper launch: isotropic drives whose diagonal a reversed body took ONCE before the sub-step loop, aba_fetch_diso): the torque alone.
+PHC_HD void aba_publish_drive(const AbaLane& L, int j, const Xch& x, bool tau_only = false) {
     constexpr int es = Xch::es;
     float* s = xslot(x, j);
     s[19 * es] = L.tau_w.x; s[20 * es] = L.tau_w.y; s[21 * es] = L.tau_w.z;
+    if (tau_only) return;
     const bool iso = L.diso >= 0.f;
     s[22 * es] = iso ? L.diso : L.Dw.xx; s[23 * es] = iso ? 0.f : L.Dw.xy; s[24 * es] = iso ? 0.f : L.Dw.xz;
     s[25 * es] = iso ? L.diso : L.Dw.yy; s[26 * es] = iso ? 0.f : L.Dw.yz; s[27 * es] = iso ? L.diso : L.Dw.zz;
 }
-PHC_HD void aba_fetch_drive(AbaLane& L, int j, const Xch& x) {
+PHC_HD void aba_fetch_drive(AbaLane& L, int j, const Xch& x, bool tau_only = false) {
     if (L.jsrc < 0 || L.jsrc == j) return;
     constexpr int es = Xch::es;
     const float* s = xslot(x, L.jsrc);
     L.tau_w = v3(-s[19 * es], -s[20 * es], -s[21 * es]);
+    if (tau_only) return;
     L.Dw.xx = s[22 * es]; L.Dw.xy = s[23 * es]; L.Dw.xz = s[24 * es]; L.Dw.yy = s[25 * es]; L.Dw.yz = s[26 * es]; L.Dw.zz = s[27 * es];
     const bool iso = L.Dw.xy == 0.f && L.Dw.xz == 0.f && L.Dw.yz == 0.f && L.Dw.xx == L.Dw.yy && L.Dw.yy == L.Dw.zz;
     L.diso = iso ? L.Dw.xx : -1.f;
+}
+// once per launch (isotropic drives): every body publishes its joint's diagonal at slot [22], a reversed body then takes its solver parent's
+PHC_HD void aba_publish_diso(const AbaLane& L, int j, const Xch& x) { xslot(x, j)[22 * Xch::es] = L.diso; }
+PHC_HD void aba_fetch_diso(AbaLane& L, int j, const Xch& x) {
+    if (L.jsrc < 0 || L.jsrc == j) return;
+    L.diso = xslot(x, L.jsrc)[22 * Xch::es];
 }
 // After the acceleration sweep: what aba_integrate_joint reads from L.u / L.ca.  A joint solved by a reversed body gets that body's
 // relative acceleration with the opposite sign (beta_c = alpha_c - alpha_p - w_p x w_c = -(alpha_p - alpha_c - w_c x w_p)); the

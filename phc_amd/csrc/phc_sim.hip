@@ -56,7 +56,27 @@ extern "C" int32_t phc_debug_timeline(unsigned long long* out512, int32_t block)
 #include "phc_sim_kernel.h"
 #include "phc_sim_check.h"
 
+// the instrumented library stamps the generic kernel only
+#ifdef PHC_SIM_PROFILE
+int32_t g_phc_sim_force_generic = 1;
+#else
+int32_t g_phc_sim_force_generic = 0;
+#endif
+
 extern "C" {
+
+int32_t phc_sim_force_generic(int32_t on) {
+    const int32_t old = g_phc_sim_force_generic;
+    g_phc_sim_force_generic = on ? 1 : 0;
+    return old;
+}
+
+int32_t phc_sim_model_facts(const phc_model_t* model_on_host) { return sim_model_facts(model_on_host); }
+
+int32_t phc_sim_is_plain(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim, const float* actions, const int32_t* freeze_mask,
+                         int32_t num_sim_calls) {
+    return sim_is_plain(model, params, sim, actions, freeze_mask, num_sim_calls) ? 1 : 0;
+}
 
 int32_t phc_sim_step(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim, const float* actions,
                      const float* pd_action_offset, const float* pd_action_scale, const int32_t* freeze_mask,

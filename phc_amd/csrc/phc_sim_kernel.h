@@ -1,12 +1,13 @@
 // phc_sim_kernel.h -- k_sim_step, the articulated-body stepper kernel (S10), and what it is made of outside phc_aba.h: the action -> PD-target map and the staged
-// epilogue; behind the kernel, the chooser of the instantiation to launch.  A header because the kernel is instantiated in two translation units that are compiled with the same flags (phc_amd/build.py): phc_sim.hip holds every
-// instantiation phc_sim_step and the refresh entry points launch, phc_sim_wrench.hip the WRENCH twins of phc_sim_step_wrench.  Two units, so that adding the twins
+// epilogue; behind the kernel, the chooser of the instantiation to launch.  A header because the kernel is instantiated in three translation units that are compiled with the same flags (phc_amd/build.py): phc_sim.hip holds every
+// instantiation phc_sim_step and the refresh entry points launch, phc_sim_wrench.hip the WRENCH twins of phc_sim_step_wrench, phc_sim_plain.hip the PLAIN instantiation of the default SMPL launch.  Separate units, so that adding the twins
 // leaves the instruction streams of the plain instantiations exactly what they were (the compiler's output for one kernel depends on what else its module holds;
 // profiles/ext_wrench/README.md).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "phc_aba.h"
+#include "phc_sim_plain.h"
 
 using namespace phc;
 
@@ -140,10 +141,43 @@ __device__ __forceinline__ bool stage_aligned(const phc_sim_state_t& sim) {
 // Alternatives, by the compiler's resource report (same README): the wrench applied behind aba_body_init spills in the lagged revolute twins and, read there as
 // well, in the rigid spherical ones; a per-lane LDS slot (1.5 KB) takes the penalty / spherical workgroup from 19200 to 20736 bytes, and eight of those per CU no
 // longer fit the 160 KB.  The two lagged revolute twins needed one register more than they had: WRENCH_TIGHT below.
+// PLAIN: the instantiation of the default SMPL task's launch (phc_sim_plain.h; instantiated once, in phc_sim_plain.hip, for <true, SPHERICAL, 32, false, false, 2,
+// LAG = true, WRENCH = false>).  pin_sim_plain turns every launch option and nullable pointer of that list into a constant, SimPlainModel the body / DoF counts and the
+// solver-tree constants the generic kernel reads from the model table; what is fixed for the whole launch --
+// the implicit drive diagonals dt kd + dt^2 kp (+ armature) and kd + dt kp -- is formed once in front of the sub-step loop instead of in each of its four passes
+// (aba_plain_drive; a reversed body takes its solver parent's diagonal there, so that the drive exchange of a sub-step moves the torque alone); and the two sub-steps
+// of a simulate() call are one loop body, so that `lag` and the sub-step's parity are constants in each half (SIM_PL_LAG_PAIR).
+// Every line this adds stands behind `PLAIN`: the other instantiations are, instruction for instruction, what they were (profiles/stepper_plain_instantiation/README.md).
+// PHC_SIM_PLAIN_ITEMS: which items the plain kernel is built with -- all of them in the product; the "new minus one item" libraries of that README are built with
+// one bit cleared (0: the pins alone).
+#define SIM_PL_LAG_PAIR 8   // (behind the ABA_PL_* bits of phc_aba.h)
+#ifndef PHC_SIM_PLAIN_ITEMS
+#define PHC_SIM_PLAIN_ITEMS (ABA_PL_NO_CP_TAIL | ABA_PL_DRIVE_CONST | SIM_PL_LAG_PAIR)
+#endif
+template <bool PLAIN>
+__device__ __forceinline__ void pin_sim_plain(phc_sim_params_t& prm, phc_sim_state_t& sim, const float* __restrict__& actions, const int32_t* __restrict__& freeze,
+                                              int& num_sim_calls) {
+    if constexpr (PLAIN) {
+#define PHC_PIN_prm(f) prm.f
+#define PHC_PIN_sim(f) sim.f
+#define PHC_PIN_arg(f) f
+#define PHC_PIN_VAL(s, f, v) PHC_PIN_##s(f) = (v);
+#define PHC_PIN_NUL(s, f) PHC_PIN_##s(f) = nullptr;
+#define PHC_PIN_SET(s, f) __builtin_assume(PHC_PIN_##s(f) != nullptr);
+        PHC_SIM_PLAIN_FIELDS(PHC_PIN_VAL, PHC_PIN_NUL, PHC_PIN_SET)
+#undef PHC_PIN_VAL
+#undef PHC_PIN_NUL
+#undef PHC_PIN_SET
+#undef PHC_PIN_prm
+#undef PHC_PIN_sim
+#undef PHC_PIN_arg
+    }
+}
+
 template <bool WRENCH> struct WrenchArgs {};
 template <> struct WrenchArgs<true> { const float* force; const float* torque; int nsub; };   // [N, NB, 3] each (nullable); sub-steps the wrench acts in
 
-template <bool STEP, int JT, int GRP, bool SHAPES = false, bool RIGID = false, int OCC = 2, bool LAG = false, bool WRENCH = false>
+template <bool STEP, int JT, int GRP, bool SHAPES = false, bool RIGID = false, int OCC = 2, bool LAG = false, bool WRENCH = false, bool PLAIN = false>
 __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc_sim_params_t prm, phc_sim_state_t sim,
                                                 const float* __restrict__ actions, const float* __restrict__ pd_off,
                                                 const float* __restrict__ pd_scale, const int32_t* __restrict__ freeze,
@@ -159,6 +193,9 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     // the lagged revolute twins (see WRENCH above): aba_body_init gets a time step the compiler cannot see through, so that what it derives from dt alone is formed
     // where it is used instead of being held in a register across the sub-step loop
     constexpr bool WRENCH_TIGHT = WRENCH && LAG && JT == PHC_JT_REVOLUTE;
+    static_assert(!PLAIN || (STEP && JT == PHC_JT_SPHERICAL && GRP == 32 && !SHAPES && !RIGID && OCC == 2 && LAG && !WRENCH), "the one plain instantiation");
+    constexpr int PL = PLAIN ? (PHC_SIM_PLAIN_ITEMS) : 0;   // (phc_aba.h ABA_PL_*)
+    pin_sim_plain<PLAIN>(prm, sim, actions, freeze, num_sim_calls);
     const int lane = threadIdx.x & (GRP - 1);
     const int grp = threadIdx.x / GRP;
     const int64_t slot = (int64_t)blockIdx.x * (64 / GRP) + grp;
@@ -167,7 +204,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     // SHAPES (per-env body shapes): the env's block of the model tables -- a per-lane pointer pair; the single-shape instantiation keeps the
     // tables behind scalar registers (with the select compiled in unconditionally the kernel spilled 188 B / lane: 35 MB of scratch traffic)
     const phc_model_t model = SHAPES ? model_for_env(model_all, sim, env) : model_all;
-    const int nb = model.num_bodies, nd = model.num_dof;
+    const int nb = PLAIN ? SimPlainModel::num_bodies : model.num_bodies, nd = PLAIN ? SimPlainModel::num_dof : model.num_dof;
     const bool active = env < sim.num_envs && lane < nb;
     const int body = lane;   // one lane per body, in the model's body order
     Xch x;
@@ -196,11 +233,11 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
         }
     }
     // the idle lanes behind the bodies publish the extra collision shapes (phc_aba.h): their capsule records are loaded once, here
-    const bool shape_lane = active || (STEP && prm.self_collision && env < sim.num_envs && lane < nb + model_num_extra_shapes(model));
+    const bool shape_lane = active || (STEP && prm.self_collision && env < sim.num_envs && lane < nb + (PLAIN ? SimPlainModel::extra_shapes : model_num_extra_shapes(model)));
     if (shape_lane && !active) aba_load_extra_shape(L, model, lane - nb);
     // initial kinematics by pointer jumping too (round 4: 4 composition steps instead of max_level + 1 = 9 level-steps for the SMPL tree)
     if (!PHC_SKIP(8)) {
-        const int jsteps = model_jump_steps(model);
+        const int jsteps = PLAIN ? SimPlainModel::jump_steps : model_jump_steps(model);
         aba_fk_jump_begin(L, body, x);
         __syncthreads();
         for (int k = 0; k < jsteps; ++k) {
@@ -219,9 +256,21 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
         uint32_t near_pairs = 0;
         if (prm.self_collision) aba_load_pairs<PHC_SC_MAX_PER_LANE>(pair_all + threadIdx.x, 64, model, lane, GRP);
         // the backward / acceleration sweeps walk the solver tree (model.py solver_tree(): re-rooted where that makes it shallower)
-        const int solver_depth = model_solver_depth(model, true);
-        const int jump_steps = model_jump_steps(model);
-        const bool rerooted = model_tab(model, 11, 3) != 0;
+        const int solver_depth = PLAIN ? SimPlainModel::solver_depth : model_solver_depth(model, true);
+        const int jump_steps = PLAIN ? SimPlainModel::jump_steps : model_jump_steps(model);
+        const bool rerooted = PLAIN ? SimPlainModel::rerooted != 0 : model_tab(model, 11, 3) != 0;
+        // the plain launch: what the drive needs and no sub-step changes, once (aba_plain_drive); a reversed body takes its solver parent's diagonal
+        constexpr int SUBSTEP_UNROLL = (PL & SIM_PL_LAG_PAIR) ? 2 : 1;
+        AbaPlainDrive pdrive;
+        if constexpr ((PL & ABA_PL_DRIVE_CONST) != 0) {
+            if (active && L.level > 0) aba_plain_drive(L, pdrive, model_body(model, body), dt);
+            if (active) { if (L.level == 0) L.diso = 0.f; aba_publish_diso(L, body, x); }
+            __syncthreads();
+            if (active) aba_fetch_diso(L, body, x);
+            __syncthreads();
+        }
+        // (SIM_PL_LAG_PAIR: the two sub-steps of a simulate() call as one loop body, so that `lag` and the sub-step's parity are constants in each half)
+#pragma unroll SUBSTEP_UNROLL
         for (int s = 0; s < nsub; ++s) {
             const int tl_sub = s; (void)tl_sub;
             PHC_TL(1)
@@ -263,6 +312,9 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
                     if (!BATCH) aba_body_init<JT, RIGID>(L, model, prm, dt_b, body, s % prm.substeps == 0, true, pass, lag, ext_on, ext_f, ext_t);
                     else aba_body_init<JT, RIGID>(L, model, prm, dt_b, body, s % prm.substeps == 0, model_body(model, body), L.cp_range & 0xffff, L.cp_range >> 16, true, pass, lag,
                                                   ext_on, ext_f, ext_t);
+                } else if constexpr (PLAIN) {
+                    aba_body_init<JT, RIGID, PL>(L, model, prm, dt, body, s % prm.substeps == 0, model_body(model, body), L.cp_range & 0xffff, L.cp_range >> 16, true, pass, lag,
+                                                 false, V3(), V3(), &pdrive);
                 } else {
                 if (!BATCH) aba_body_init<JT, RIGID>(L, model, prm, dt, body, s % prm.substeps == 0, true, pass, lag);
                 else aba_body_init<JT, RIGID>(L, model, prm, dt, body, s % prm.substeps == 0, model_body(model, body), L.cp_range & 0xffff, L.cp_range >> 16, true, pass, lag);
@@ -272,14 +324,14 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             PHC_PROF(2)
             PHC_TL(4)
             if (JT == PHC_JT_SPHERICAL && rerooted && pass == 0 && !PHC_SKIP(2)) {   // reversed bodies take the drive terms of their solver parent's joint
-                if (active) aba_publish_drive(L, body, x);
+                if (active) aba_publish_drive(L, body, x, (PL & ABA_PL_DRIVE_CONST) != 0);
                 __syncthreads();
-                if (active) aba_fetch_drive(L, body, x);
+                if (active) aba_fetch_drive(L, body, x, (PL & ABA_PL_DRIVE_CONST) != 0);
                 __syncthreads();
             }
             PHC_PROF(3)
             PHC_TL(5)
-            if (!PHC_SKIP(3)) for (int l = solver_depth; l >= 0; --l) { aba_backward_level<JT>(L, l, body, x, lag); __syncthreads(); PHC_TL(120 + l) }
+            if (!PHC_SKIP(3)) for (int l = solver_depth; l >= 0; --l) { aba_backward_level<JT, (PL & ABA_PL_DRIVE_CONST) != 0>(L, l, body, x, lag); __syncthreads(); PHC_TL(120 + l) }
             PHC_PROF(4)
             if (!PHC_SKIP(4)) {
                 for (int l = 0; l <= solver_depth; ++l) { aba_accel_level<JT>(L, l, body, x); __syncthreads(); PHC_TL(140 + l) }
@@ -311,7 +363,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     const int64_t env0 = (int64_t)blockIdx.x * E;
     const StageLayout so = stage_layout(E, nb, nd, sim.dof_force != nullptr, sim.contact_force != nullptr);
     if (PHC_SKIP(7)) {
-    } else if (STEP && E >= 2 && env0 + E <= sim.num_envs && stage_aligned(sim) && so.total <= 64 * PHC_XCH_STRIDE) {   // staged epilogue, see above
+    } else if (STEP && E >= 2 && env0 + E <= sim.num_envs && (PLAIN || stage_aligned(sim)) && so.total <= 64 * PHC_XCH_STRIDE) {   // staged epilogue, see above
         const phc_sim_state_t st = stage_state(sim, xch_all, so);
         if (active) {
             aba_store_state<JT>(L, st, nd, grp, body);
@@ -332,6 +384,14 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
 // The launch chooser: which instantiation a model and its options run.  One chooser for both translation units; WRENCH = true names only the instantiations
 // phc_sim_step_wrench launches (one env-shape block, two wavefronts per SIMD: it refuses the rest), so each unit holds exactly its own kernels.
 // ------------------------------------------------------------------------------------------
+// phc_sim_force_generic (include/phc_amd.h): the process-wide host switch that sends plain launches through the generic kernel too; defined in phc_sim.hip
+extern int32_t g_phc_sim_force_generic;
+// the plain instantiation lives in phc_sim_plain.hip
+extern template __global__ void k_sim_step<true, PHC_JT_SPHERICAL, 32, false, false, 2, true, false, true>(phc_model_t, phc_sim_params_t, phc_sim_state_t, const float* __restrict__,
+                                                                                                           const float* __restrict__, const float* __restrict__,
+                                                                                                           const int32_t* __restrict__, int, const int64_t* __restrict__, int,
+                                                                                                           WrenchArgs<false>);
+
 template <bool STEP, int JT, bool SHAPES, bool RIGID, bool WRENCH>
 static void sim_launch_cm(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions, const float* off,
                           const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream, const int64_t* env_ids, int num_listed,
@@ -345,6 +405,9 @@ static void sim_launch_cm(const phc_model_t* model, const phc_sim_params_t& prm,
     };
     if constexpr (!WRENCH && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // (experiment knob, see OCC above)
         if (!wide && prm.lane_mapping == 3) return launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 3>, (groups + 1) / 2);
+    if constexpr (STEP && !WRENCH && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // the plain launch: every entry of phc_sim_plain.h holds (and the switch is off)
+        if (lag && !wide && !g_phc_sim_force_generic && sim_is_plain(model, &prm, sim, actions, freeze, num_sim_calls))
+            return launch(k_sim_step<true, PHC_JT_SPHERICAL, 32, false, false, 2, true, false, true>, (groups + 1) / 2);
     if (lag && wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, LAG, WRENCH>, groups);
     else if (lag) launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, LAG, WRENCH>, (groups + 1) / 2);
     else if (wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, false, WRENCH>, groups);
