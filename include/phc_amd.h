@@ -708,6 +708,58 @@ typedef struct {
 } phc_push_args_t;
 int32_t phc_push_advance(const phc_push_args_t* args /* host */, void* stream);
 
+/* Domain randomisation in the stepper (csrc/phc_sim_dr.hip, the DR instantiations of the stepper's kernel; per-lane code csrc/phc_dr.h; additions to ABI 37, which
+ * stays 37): phc_sim_step with PER-ENV physics.  With `dr` NULL, or both of its tensors NULL, and a model phc_sim_step accepts, the call IS phc_sim_step: same
+ * checks, same launch, same bits.
+ *   model blocks   model->num_shapes > 1 with sim->env_shape is accepted for BOTH joint families here (phc_sim_step keeps refusing revolute models): env i steps
+ *                  with block env_shape[i] of the int / float tables -- its own masses, centres of mass, inertias, gains.  The blocks share topology and geometry;
+ *                  the caller guarantees that (the check cannot read device memory);
+ *   env_friction   env i's Coulomb coefficient max(env_friction[i], 0) replaces params->friction in every place the stepper reads it (penalty points, rigid
+ *                  contact, force sensors);
+ *   torque_noise   revolute models under control_mode 1 / 2: at the first sub-step of simulate call c of the launch, DoF d of env i steps with the PD target
+ *                  target + u amp[i, d] / kp, u = dr_noise_u(key, k[i], c, (env_offset + i) D + d) in [-1, 1) -- a torque u amp added in front of the effort
+ *                  clip (and of mode 2's saturation test).  kp is the env's block's; a DoF with kp == 0 gets none.  The published pd_target stays the un-noised one.
+ * PHC_EUNSUPPORTED: lane_mapping 3; torque_noise on a spherical model or with control_mode 0.  PHC_EINVAL: torque_noise without k, env_offset < 0 or
+ * (env_offset + N) D > 2^32, num_shapes > 1 without env_shape; then everything phc_sim_step refuses.  No external wrench in this launch. */
+typedef struct {
+    const float*   env_friction;   /* [N]; nullable */
+    const float*   torque_noise;   /* [N, D] amplitude in N m; nullable */
+    const int32_t* k;              /* [N] env-step counter of each env (written by phc_dr_advance); required with torque_noise */
+    uint64_t       key;            /* stream key */
+    int64_t        env_offset;     /* global index of env 0 (ranks of one run draw disjoint streams) */
+} phc_sim_dr_t;
+int32_t phc_sim_step_dr(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim, const float* actions,
+                        const float* pd_action_offset, const float* pd_action_scale, const int32_t* freeze_mask, int32_t num_sim_calls,
+                        const phc_sim_dr_t* dr /* host; nullable */, void* stream);
+
+/* The per-env-step part of domain randomisation (csrc/phc_dr.hip, per-lane code csrc/phc_dr.h; an addition to ABI 37): control delay and velocity pushes, one
+ * launch per env step AHEAD of the stepper, one lane per env.  All state and draws live on the device: a captured launch moves on with every replay.  Per env i,
+ * with k = k[i] and Q = delay_hi + 1:
+ *   reset  = k == 0 or progress_buf[i] == 0: the env's Q rows of the queue are zeroed and delay[i] = delay_lo + min(floor(u (delay_hi - delay_lo + 1)),
+ *            delay_hi - delay_lo) is drawn anew;
+ *   actions[i] goes to row k mod Q, row (k - delay[i]) mod Q goes to delayed_actions[i] (delay_hi == 0: delayed_actions[i] = actions[i], no queue);
+ *   push_interval > 0, k > 0, k % push_interval == 0 and the env was not just reset: root_states[i, 7:9] = two draws of U(-max_push_vel_xy, max_push_vel_xy);
+ *   k[i] += 1.
+ * Integer state and draws are bit-equal to the host build of phc_dr.h.  PHC_EINVAL before any device work: a null args / actions / delayed_actions / delay / k,
+ * a null action_queue with delay_hi > 0, a null root_states with push_interval > 0, num_envs < 0, num_dof < 1, delay_lo < 0, delay_hi < delay_lo or > 1023,
+ * push_interval < 0, max_push_vel_xy negative or not finite, env_offset < 0 or env_offset + num_envs > 2^32.  num_envs == 0 returns 0 without a launch. */
+typedef struct {
+    int32_t num_envs, num_dof;
+    int32_t delay_lo, delay_hi;          /* env steps, inclusive */
+    int32_t push_interval;               /* env steps; 0 = no velocity push */
+    float   max_push_vel_xy;
+    uint64_t key;
+    int64_t env_offset;
+    const int64_t* progress_buf;         /* [N]; nullable = no env was reset */
+    const float* actions;                /* [N, D] */
+    float*   action_queue;               /* [Q, N, D] ring */
+    int32_t* delay;                      /* [N] */
+    int32_t* k;                          /* [N] launches the env has seen */
+    float*   delayed_actions;            /* [N, D] out: what the stepper is given */
+    float*   root_states;                /* [N, 13]; nullable unless push_interval > 0 */
+} phc_dr_args_t;
+int32_t phc_dr_advance(const phc_dr_args_t* args /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,16 @@ class PushArgs(C.Structure):
 
 
 P = C.POINTER
+class SimDr(C.Structure):
+    _fields_ = [("env_friction", c_p), ("torque_noise", c_p), ("k", c_p), ("key", C.c_uint64), ("env_offset", c_i64)]
+
+
+class DrArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_dof", c_i32), ("delay_lo", c_i32), ("delay_hi", c_i32), ("push_interval", c_i32), ("max_push_vel_xy", c_f),
+                ("key", C.c_uint64), ("env_offset", c_i64), ("progress_buf", c_p), ("actions", c_p), ("action_queue", c_p), ("delay", c_p), ("k", c_p),
+                ("delayed_actions", c_p), ("root_states", c_p)]
+
+
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
@@ -172,6 +182,8 @@ _OPTIONAL_SIGNATURES = {
     "phc_sim_model_facts": ([P(Model)], c_i32),
     "phc_sim_is_plain": ([P(Model), P(SimParams), P(SimState), c_p, c_p, c_i32], c_i32),
     "phc_sim_force_generic": ([c_i32], c_i32),
+    "phc_sim_step_dr": ([P(Model), P(SimParams), P(SimState), c_p, c_p, c_p, c_p, c_i32, P(SimDr), c_p], c_i32),
+    "phc_dr_advance": ([P(DrArgs), c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

@@ -140,6 +140,24 @@ _CONTROL_DEFAULT = {"action_filter": False, "action_scale": 1, "decimation": 2, 
 _DR_DEFAULT = {"has_domain_rand": False, "push_robots": False, "randomize_friction": False, "randomize_base_mass": False,
                "randomize_base_com": False, "randomize_link_mass": False, "randomize_pd_gain": False, "randomize_torque_rfi": False,
                "randomize_ctrl_delay": False, "add_noise": False}
+# domain_rand/h1_dr.yaml: the physical randomisation the reference trains the Unitree robots under (phc_amd/domain_rand.py applies it)
+_DR_H1 = {
+    "has_domain_rand": True, "push_robots": True, "push_interval_s": 5, "max_push_vel_xy": 0.3,
+    "randomize_friction": True, "friction_range": [-0.6, 1.2],
+    "randomize_base_mass": False, "added_mass_range": [-5.0, 10.0],
+    "randomize_base_com": True, "base_com_range": {"x": [-0.1, 0.1], "y": [-0.1, 0.1], "z": [-0.2, 0.2]},
+    "randomize_link_mass": True, "link_mass_range": [0.7, 1.3],
+    "randomize_link_body_names": ["pelvis", "left_hip_yaw_link", "left_hip_roll_link", "left_hip_pitch_link",
+                                  "right_hip_yaw_link", "right_hip_roll_link", "right_hip_pitch_link", "torso_link"],
+    "randomize_pd_gain": True, "kp_range": [0.75, 1.25], "kd_range": [0.75, 1.25],
+    "randomize_torque_rfi": True, "rfi_lim": 0.1, "randomize_rfi_lim": False, "rfi_lim_range": [0.5, 1.5],
+    "randomize_ctrl_delay": True, "ctrl_delay_step_range": [1, 3],
+    "add_noise": True, "noise_level": 1.0,
+    "noise_scales": {"base_z": 0.05, "dof_pos": 0.01, "dof_vel": 0.1, "lin_vel": 0.2, "ang_vel": 0.5, "gravity": 0.1, "in_contact": 0.1,
+                     "height_measurements": 0.05, "body_pos": 0.01, "body_lin_vel": 0.01, "body_rot": 0.001, "delta_base_pos": 0.05,
+                     "delta_heading": 0.1, "last_action": 0.0, "ref_body_pos": 0.05, "ref_body_rot": 0.01, "ref_lin_vel": 0.01,
+                     "ref_ang_vel": 0.01, "ref_dof_pos": 0.01, "ref_dof_vel": 0.01, "ref_gravity": 0.01},
+}
 
 
 def _learning(units, activation, net_name="amp", extra_cfg=None, extra_net=None):
@@ -193,7 +211,7 @@ GROUPS = {
                                          {"has_softmax": False, "ending_act": True})},
     "sim": {"default_sim": _SIM_DEFAULT, "robot_sim": _SIM_ROBOT},
     "control": {"default_control": _CONTROL_DEFAULT, "robot_control": dict(_CONTROL_DEFAULT, decimation=4, control_mode="pd")},
-    "domain_rand": {"default_dr": _DR_DEFAULT},
+    "domain_rand": {"default_dr": _DR_DEFAULT, "h1_dr": _DR_H1},
 }
 
 

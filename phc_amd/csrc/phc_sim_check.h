@@ -42,4 +42,21 @@ inline int32_t check_sim_step_wrench(const phc_model_t* model, const phc_sim_par
     return check_sim_step(model, params, sim, actions, pd_action_offset, pd_action_scale, num_sim_calls);
 }
 
+// a stepping launch with domain randomisation (phc_sim_step_dr): what it refuses ahead of check_sim_step, and the one thing it accepts that check_sim_step does
+// not -- env-shape blocks of a revolute model (the blocks' strides are checked here, the rest of the model as one block)
+inline int32_t check_sim_step_dr(const phc_model_t* model, const phc_sim_params_t* params, const phc_sim_state_t* sim, const float* actions,
+                                 const float* pd_action_offset, const float* pd_action_scale, int32_t num_sim_calls, const phc_sim_dr_t* dr) {
+    if (params && params->lane_mapping == 3) return PHC_EUNSUPPORTED;   // the three-wavefront experiment build has no DR twin
+    if (!model) return PHC_EINVAL;
+    const bool revolute = model->num_dof == model->num_bodies - 1 && model->num_bodies > 2;
+    if (dr && dr->torque_noise && (!revolute || (params && params->control_mode == 0))) return PHC_EUNSUPPORTED;   // the target shift is the explicit drives' identity
+    if (dr && dr->torque_noise && !dr->k) return PHC_EINVAL;
+    if (dr && sim && (dr->env_offset < 0 || dr->env_offset > ((int64_t)1 << 32) || sim->num_envs < 0 ||
+                      (dr->env_offset + (int64_t)sim->num_envs) * (int64_t)(model->num_dof > 0 ? model->num_dof : 1) > (int64_t)1 << 32)) return PHC_EINVAL;
+    if (model->num_shapes > 1 && (model->int_stride <= 0 || model->float_stride <= 0 || !sim || !sim->env_shape)) return PHC_EINVAL;
+    phc_model_t one = *model;
+    one.num_shapes = 1;
+    return check_sim_step(&one, params, sim, actions, pd_action_offset, pd_action_scale, num_sim_calls);
+}
+
 }  // namespace phc

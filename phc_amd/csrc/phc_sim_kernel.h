@@ -1,6 +1,6 @@
 // phc_sim_kernel.h -- k_sim_step, the articulated-body stepper kernel (S10), and what it is made of outside phc_aba.h: the action -> PD-target map and the staged
-// epilogue; behind the kernel, the chooser of the instantiation to launch.  A header because the kernel is instantiated in three translation units that are compiled with the same flags (phc_amd/build.py): phc_sim.hip holds every
-// instantiation phc_sim_step and the refresh entry points launch, phc_sim_wrench.hip the WRENCH twins of phc_sim_step_wrench, phc_sim_plain.hip the PLAIN instantiation of the default SMPL launch.  Separate units, so that adding the twins
+// epilogue; behind the kernel, the chooser of the instantiation to launch.  A header because the kernel is instantiated in four translation units that are compiled with the same flags (phc_amd/build.py): phc_sim.hip holds every
+// instantiation phc_sim_step and the refresh entry points launch, phc_sim_wrench.hip the WRENCH twins of phc_sim_step_wrench, phc_sim_plain.hip the PLAIN instantiation of the default SMPL launch, phc_sim_dr.hip the DR twins of phc_sim_step_dr.  Separate units, so that adding the twins
 // leaves the instruction streams of the plain instantiations exactly what they were (the compiler's output for one kernel depends on what else its module holds;
 // profiles/ext_wrench/README.md).
 #pragma once
@@ -8,6 +8,7 @@
 #include <type_traits>
 #include "phc_aba.h"
 #include "phc_sim_plain.h"
+#include "phc_dr.h"
 
 using namespace phc;
 
@@ -177,11 +178,22 @@ __device__ __forceinline__ void pin_sim_plain(phc_sim_params_t& prm, phc_sim_sta
 template <bool WRENCH> struct WrenchArgs {};
 template <> struct WrenchArgs<true> { const float* force; const float* torque; int nsub; };   // [N, NB, 3] each (nullable); sub-steps the wrench acts in
 
-template <bool STEP, int JT, int GRP, bool SHAPES = false, bool RIGID = false, int OCC = 2, bool LAG = false, bool WRENCH = false, bool PLAIN = false>
+// DR: the instantiations of phc_sim_step_dr (per-env friction, per-env model blocks for both joint families, torque noise; include/phc_amd.h; launched from
+// phc_sim_dr.hip) -- a template parameter for the reason LAG and WRENCH are.  Its kernel arguments exist in these instantiations only (DrArgs<false> is empty)
+// and every line it adds stands behind `if constexpr (DR)`.  Friction: each call into phc_aba.h that reads prm.friction gets a copy of the parameter struct
+// that carries the env's coefficient (dr_params below), so no signature of phc_aba.h changes.  Torque noise (revolute, control_mode 1 / 2): at the first
+// sub-step of a simulate call the lane's PD target is the un-noised one + u amp / kp (phc_dr.h) -- aba_body_init samples the spring there and nowhere else.
+// DR twins are SHAPES twins: the env's block of the model tables is a per-lane pointer pair whether the launch has one block or many.  All twelve keep two
+// wavefronts per SIMD; their scratch (the publishers' indexed parameter copies; 8 - 10 spilled VGPRs in the lagged revolute twins) is in
+// profiles/domain_rand/README.md.
+template <bool DR> struct DrArgs {};
+template <> struct DrArgs<true> { const float* env_friction; const float* torque_noise; const int32_t* k; uint64_t key; int64_t env_offset; };   // (phc_sim_dr_t)
+
+template <bool STEP, int JT, int GRP, bool SHAPES = false, bool RIGID = false, int OCC = 2, bool LAG = false, bool WRENCH = false, bool PLAIN = false, bool DR = false>
 __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc_sim_params_t prm, phc_sim_state_t sim,
                                                 const float* __restrict__ actions, const float* __restrict__ pd_off,
                                                 const float* __restrict__ pd_scale, const int32_t* __restrict__ freeze,
-                                                int num_sim_calls, const int64_t* __restrict__ env_ids, int num_listed, WrenchArgs<WRENCH> wr) {
+                                                int num_sim_calls, const int64_t* __restrict__ env_ids, int num_listed, WrenchArgs<WRENCH> wr, DrArgs<DR> dr) {
     __shared__ __attribute__((aligned(16))) float xch_all[64 * PHC_XCH_STRIDE];   // one exchange slot per lane == body (16-byte aligned: the lagged hand-over moves as b128 + b64)
     __shared__ float cap_all[64 * PHC_CAP_STRIDE];
     __shared__ int pair_all[PHC_SC_MAX_PER_LANE * 64];   // candidate pairs of body-body contact: [pair slot][thread]
@@ -193,6 +205,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     // the lagged revolute twins (see WRENCH above): aba_body_init gets a time step the compiler cannot see through, so that what it derives from dt alone is formed
     // where it is used instead of being held in a register across the sub-step loop
     constexpr bool WRENCH_TIGHT = WRENCH && LAG && JT == PHC_JT_REVOLUTE;
+    static_assert(!DR || (STEP && SHAPES && OCC == 2 && !WRENCH && !PLAIN), "the DR twins");
     static_assert(!PLAIN || (STEP && JT == PHC_JT_SPHERICAL && GRP == 32 && !SHAPES && !RIGID && OCC == 2 && LAG && !WRENCH), "the one plain instantiation");
     constexpr int PL = PLAIN ? (PHC_SIM_PLAIN_ITEMS) : 0;   // (phc_aba.h ABA_PL_*)
     pin_sim_plain<PLAIN>(prm, sim, actions, freeze, num_sim_calls);
@@ -204,6 +217,11 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     // SHAPES (per-env body shapes): the env's block of the model tables -- a per-lane pointer pair; the single-shape instantiation keeps the
     // tables behind scalar registers (with the select compiled in unconditionally the kernel spilled 188 B / lane: 35 MB of scratch traffic)
     const phc_model_t model = SHAPES ? model_for_env(model_all, sim, env) : model_all;
+    // the env's own friction coefficient.  It reaches phc_aba.h in a copy of the parameters made at each call that reads prm.friction (dr_params): a copy the
+    // sub-step loop uses is never indexed, so it lives in registers; the ones the publishers index (force_sensor_body[k]) are stack objects touched once per launch
+    float dr_friction = 0.f;
+    if constexpr (DR) dr_friction = (dr.env_friction != nullptr && env < sim.num_envs) ? fmaxf(dr.env_friction[env], 0.f) : prm.friction;
+    auto dr_params = [&]() { phc_sim_params_t p = prm; p.friction = dr_friction; return p; };
     const int nb = PLAIN ? SimPlainModel::num_bodies : model.num_bodies, nd = PLAIN ? SimPlainModel::num_dof : model.num_dof;
     const bool active = env < sim.num_envs && lane < nb;
     const int body = lane;   // one lane per body, in the model's body order
@@ -230,6 +248,14 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
 #pragma unroll
             for (int k = 0; k < K; ++k) sim.pd_target[env * nd + L.dof_start + k] = tg[k];   // (stored after all K are formed: no load waits behind a store)
             L.target = v3(tg[0], tg[1], tg[2]);
+        }
+    }
+    // torque noise: the lane's un-noised target and amp / kp (kp: the env's block), once
+    float dr_target = 0.f, dr_gain = 0.f;
+    if constexpr (DR && JT == PHC_JT_REVOLUTE) {
+        if (dr.torque_noise != nullptr && active && L.level > 0) {
+            dr_target = L.target.x;
+            dr_gain = dr_noise_gain(dr.torque_noise[env * nd + L.dof_start], model_body(model, body)[13]);
         }
     }
     // the idle lanes behind the bodies publish the extra collision shapes (phc_aba.h): their capsule records are loaded once, here
@@ -302,6 +328,11 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             // inertia_lag (round 5; penalty contact): the sub-steps behind the first one of a simulate() call keep its articulated inertias and joint-space
             // inverses and only redo the bias-force recursion (aba_body_init / aba_backward_level, `lag`)
             const bool lag = LAG && !RIGID && (s % prm.substeps) != 0;
+            if constexpr (DR && JT == PHC_JT_REVOLUTE) {   // a new simulate call: a new draw (only a joint's own lane reads; the tensors end with the last env's last DoF)
+                if (dr.torque_noise != nullptr && active && L.level > 0 && s % prm.substeps == 0)
+                    L.target.x = dr_target_shift(dr_target, dr_noise_u(dr.key, (uint32_t)dr.k[env], (uint32_t)(s / prm.substeps),
+                                                                       (uint32_t)((dr.env_offset + env) * nd + L.dof_start)), dr_gain);
+            }
             for (int pass = 0; pass < passes; ++pass) {
             PHC_TL(3)
             // (penalty contact: the body's slice of the contact-point table from the lane's registers, not from two table loads the point loads would wait for)
@@ -312,6 +343,10 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
                     if (!BATCH) aba_body_init<JT, RIGID>(L, model, prm, dt_b, body, s % prm.substeps == 0, true, pass, lag, ext_on, ext_f, ext_t);
                     else aba_body_init<JT, RIGID>(L, model, prm, dt_b, body, s % prm.substeps == 0, model_body(model, body), L.cp_range & 0xffff, L.cp_range >> 16, true, pass, lag,
                                                   ext_on, ext_f, ext_t);
+                } else if constexpr (DR) {
+                    const phc_sim_params_t pf = dr_params();
+                    if (!BATCH) aba_body_init<JT, RIGID>(L, model, pf, dt, body, s % prm.substeps == 0, true, pass, lag);
+                    else aba_body_init<JT, RIGID>(L, model, pf, dt, body, s % prm.substeps == 0, model_body(model, body), L.cp_range & 0xffff, L.cp_range >> 16, true, pass, lag);
                 } else if constexpr (PLAIN) {
                     aba_body_init<JT, RIGID, PL>(L, model, prm, dt, body, s % prm.substeps == 0, model_body(model, body), L.cp_range & 0xffff, L.cp_range >> 16, true, pass, lag,
                                                  false, V3(), V3(), &pdrive);
@@ -337,6 +372,8 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
                 for (int l = 0; l <= solver_depth; ++l) { aba_accel_level<JT>(L, l, body, x); __syncthreads(); PHC_TL(140 + l) }
             }
             }
+            if constexpr (DR) { if (RIGID && active && (s == nsub - 1 || prm.force_average)) { const phc_sim_params_t pf = dr_params(); aba_publish_contact_rigid(L, model, pf, sim, dt, env, body, true); } }
+            else
             if (RIGID && active && (s == nsub - 1 || prm.force_average)) aba_publish_contact_rigid(L, model, prm, sim, dt, env, body, true);   // S4 / S6 from the final solve
             if (JT == PHC_JT_SPHERICAL && rerooted && !PHC_SKIP(4)) aba_accel_finish(L, model, body, x, offs);
             PHC_PROF(5)
@@ -375,6 +412,8 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
         if (STEP) aba_store_state<JT>(L, sim, nd, env, body);
         aba_publish_body(L, sim, nb, env, body, STEP);
     }
+    if constexpr (DR) { if (!RIGID && active && sim.force_sensor != nullptr) { const phc_sim_params_t pf = dr_params(); aba_publish_sensors(L, model, pf, sim, prm.sim_dt / (float)prm.substeps, env, body); } }
+    else
     if (STEP && !RIGID && active && sim.force_sensor != nullptr) aba_publish_sensors(L, model, prm, sim, prm.sim_dt / (float)prm.substeps, env, body);   // S6
     PHC_PROF(8)
     if (STEP) { PHC_PROF_FLUSH }
@@ -382,57 +421,64 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
 
 // ------------------------------------------------------------------------------------------
 // The launch chooser: which instantiation a model and its options run.  One chooser for both translation units; WRENCH = true names only the instantiations
-// phc_sim_step_wrench launches (one env-shape block, two wavefronts per SIMD: it refuses the rest), so each unit holds exactly its own kernels.
+// phc_sim_step_wrench launches (one env-shape block, two wavefronts per SIMD: it refuses the rest), DR = true only the twins of phc_sim_step_dr, so each unit
+// holds exactly its own kernels.
 // ------------------------------------------------------------------------------------------
 // phc_sim_force_generic (include/phc_amd.h): the process-wide host switch that sends plain launches through the generic kernel too; defined in phc_sim.hip
 extern int32_t g_phc_sim_force_generic;
 // the plain instantiation lives in phc_sim_plain.hip
-extern template __global__ void k_sim_step<true, PHC_JT_SPHERICAL, 32, false, false, 2, true, false, true>(phc_model_t, phc_sim_params_t, phc_sim_state_t, const float* __restrict__,
+extern template __global__ void k_sim_step<true, PHC_JT_SPHERICAL, 32, false, false, 2, true, false, true, false>(phc_model_t, phc_sim_params_t, phc_sim_state_t, const float* __restrict__,
                                                                                                            const float* __restrict__, const float* __restrict__,
                                                                                                            const int32_t* __restrict__, int, const int64_t* __restrict__, int,
-                                                                                                           WrenchArgs<false>);
+                                                                                                           WrenchArgs<false>, DrArgs<false>);
 
-template <bool STEP, int JT, bool SHAPES, bool RIGID, bool WRENCH>
+template <bool STEP, int JT, bool SHAPES, bool RIGID, bool WRENCH, bool DR>
 static void sim_launch_cm(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions, const float* off,
                           const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream, const int64_t* env_ids, int num_listed,
-                          const WrenchArgs<WRENCH>& wr) {
+                          const WrenchArgs<WRENCH>& wr, const DrArgs<DR>& dr) {
     const int64_t groups = env_ids ? num_listed : sim->num_envs;
     const bool wide = model->num_bodies > 32;   // more bodies than a 32-lane group holds: one env per wavefront
     constexpr bool LAG = STEP && !RIGID;
     const bool lag = LAG && prm.inertia_lag != 0;
     auto launch = [&](auto kernel, int64_t blocks) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze, num_sim_calls, env_ids, num_listed, wr);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze, num_sim_calls, env_ids, num_listed, wr, dr);
     };
-    if constexpr (!WRENCH && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // (experiment knob, see OCC above)
+    if constexpr (!WRENCH && !DR && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // (experiment knob, see OCC above)
         if (!wide && prm.lane_mapping == 3) return launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 3>, (groups + 1) / 2);
-    if constexpr (STEP && !WRENCH && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // the plain launch: every entry of phc_sim_plain.h holds (and the switch is off)
+    if constexpr (STEP && !WRENCH && !DR && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // the plain launch: every entry of phc_sim_plain.h holds (and the switch is off)
         if (lag && !wide && !g_phc_sim_force_generic && sim_is_plain(model, &prm, sim, actions, freeze, num_sim_calls))
-            return launch(k_sim_step<true, PHC_JT_SPHERICAL, 32, false, false, 2, true, false, true>, (groups + 1) / 2);
-    if (lag && wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, LAG, WRENCH>, groups);
-    else if (lag) launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, LAG, WRENCH>, (groups + 1) / 2);
-    else if (wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, false, WRENCH>, groups);
-    else launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, false, WRENCH>, (groups + 1) / 2);
+            return launch(k_sim_step<true, PHC_JT_SPHERICAL, 32, false, false, 2, true, false, true, false>, (groups + 1) / 2);
+    if (lag && wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, LAG, WRENCH, false, DR>, groups);
+    else if (lag) launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, LAG, WRENCH, false, DR>, (groups + 1) / 2);
+    else if (wide) launch(k_sim_step<STEP, JT, 64, SHAPES, RIGID, 2, false, WRENCH, false, DR>, groups);
+    else launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 2, false, WRENCH, false, DR>, (groups + 1) / 2);
 }
 
-template <bool STEP, int JT, bool SHAPES, bool WRENCH>
+template <bool STEP, int JT, bool SHAPES, bool WRENCH, bool DR>
 static void sim_launch_jt(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions, const float* off,
                           const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream, const int64_t* env_ids, int num_listed,
-                          const WrenchArgs<WRENCH>& wr) {
+                          const WrenchArgs<WRENCH>& wr, const DrArgs<DR>& dr) {
     if (STEP && prm.contact_model == 1)   // rigid ground contact: its own instantiation, the penalty kernel is untouched by it
-        sim_launch_cm<STEP, JT, SHAPES, STEP, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+        sim_launch_cm<STEP, JT, SHAPES, STEP, WRENCH, DR>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr, dr);
     else
-        sim_launch_cm<STEP, JT, SHAPES, false, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+        sim_launch_cm<STEP, JT, SHAPES, false, WRENCH, DR>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr, dr);
 }
-template <bool STEP, bool WRENCH>
+template <bool STEP, bool WRENCH, bool DR = false>
 static void sim_launch(const phc_model_t* model, const phc_sim_params_t& prm, const phc_sim_state_t* sim, const float* actions, const float* off,
                        const float* scale, const int32_t* freeze, int num_sim_calls, hipStream_t stream, const int64_t* env_ids, int num_listed,
-                       const WrenchArgs<WRENCH>& wr) {
-    if (model->num_dof == model->num_bodies - 1 && model->num_bodies > 2)  // one revolute joint per body (robots; one shape)
-        return sim_launch_jt<STEP, PHC_JT_REVOLUTE, false, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+                       const WrenchArgs<WRENCH>& wr, const DrArgs<DR>& dr = DrArgs<DR>()) {
+    const bool revolute = model->num_dof == model->num_bodies - 1 && model->num_bodies > 2;   // one revolute joint per body (robots)
+    if constexpr (DR) {   // the DR twins: the env's block of the model tables for both joint families (one block: block 0)
+        if (revolute) return sim_launch_jt<STEP, PHC_JT_REVOLUTE, true, false, true>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr, dr);
+        return sim_launch_jt<STEP, PHC_JT_SPHERICAL, true, false, true>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr, dr);
+    } else {
+    if (revolute)  // (one shape)
+        return sim_launch_jt<STEP, PHC_JT_REVOLUTE, false, WRENCH, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr, dr);
     if constexpr (!WRENCH)
         if (model->num_shapes > 1 && sim->env_shape != nullptr)   // per-env body shapes (SMPL family)
-            return sim_launch_jt<STEP, PHC_JT_SPHERICAL, true, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
-    sim_launch_jt<STEP, PHC_JT_SPHERICAL, false, WRENCH>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr);
+            return sim_launch_jt<STEP, PHC_JT_SPHERICAL, true, false, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr, dr);
+    sim_launch_jt<STEP, PHC_JT_SPHERICAL, false, WRENCH, false>(model, prm, sim, actions, off, scale, freeze, num_sim_calls, stream, env_ids, num_listed, wr, dr);
+    }
 }
 
 static inline int32_t launch_status() {

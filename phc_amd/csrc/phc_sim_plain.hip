@@ -6,4 +6,4 @@
 template __global__ void k_sim_step<true, PHC_JT_SPHERICAL, 32, false, false, 2, true, false, true>(phc_model_t, phc_sim_params_t, phc_sim_state_t, const float* __restrict__,
                                                                                                     const float* __restrict__, const float* __restrict__,
                                                                                                     const int32_t* __restrict__, int, const int64_t* __restrict__, int,
-                                                                                                    WrenchArgs<false>);
+                                                                                                    WrenchArgs<false>, DrArgs<false>);

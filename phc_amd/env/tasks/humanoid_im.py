@@ -107,6 +107,7 @@ class HumanoidIm:
         self._load_models()
         self._setup_character_props()
         self._setup_sim_params()
+        self._setup_domain_rand()
         self._setup_im_options()
 
     # ---- host phase: load_humanoid_configs (humanoid.py:250-420) ----
@@ -426,6 +427,24 @@ class HumanoidIm:
         if cfg.get("perturb", None):
             self._check_wrench_supported("perturb")
 
+    # ---- host phase: domain randomisation (`domain_rand=h1_dr`; phc_amd/domain_rand.py): refusals and the sampler; its tensors are made with the task's ----
+    def _setup_domain_rand(self):
+        self._dr = None
+        dcfg = self.cfg.get("domain_rand", None)
+        if not dcfg or not dcfg.get("has_domain_rand", False):
+            return
+        if self.cfg.get("perturb", None):
+            raise NotImplementedError("domain_rand with +perturb.*: the stepper has no launch with both external wrenches and per-env physics")
+        if self.has_shape_variation:
+            raise NotImplementedError("domain_rand with robot.has_shape_variation: the env-shape blocks of the model carry either body shapes or DR variants")
+        if int(self._sim_params.lane_mapping) == 3:
+            raise NotImplementedError("domain_rand: not built for solver.lane_mapping=3 (the three-wavefront experiment build has no DR twin)")
+        from ...domain_rand import DomainRand
+        self._dr = DomainRand(dcfg, self.num_envs, self.model, plane_friction=float(self.cfg["env"].get("plane", {}).get("dynamicFriction", 1.0)), dt=self.dt,
+                              default_seed=int(self.cfg.get("seed", 0)), env_offset=int(self.cfg.get("rank", os.environ.get("RANK", 0))) * self.num_envs,
+                              is_robot=self._is_robot, explicit_pd=self.control_mode == "pd")
+        print(self._dr.notice())
+
     # ---- device phase: BaseTask buffers (base_task.py:62-117) ----
     def _allocate_buffers(self):
         N, dev = self.num_envs, self.device
@@ -470,6 +489,11 @@ class HumanoidIm:
         self._sim_struct = abi.sim_state_struct(N, self._root_states, self._dof_state, self._rigid_body_state, self._contact_forces,
                                                 self.dof_force_tensor, self._pd_target, force_sensor=self.vec_sensor_tensor,
                                                 env_shape=self._env_shape)
+        if self._dr is not None:   # the DR launch's own K-block model and a sim struct that names each env's block; every other consumer keeps the single block
+            self._dr.upload(dev, self._root_states, self._kp_scale, self._kd_scale)
+            self._dr_sim_struct = abi.sim_state_struct(N, self._root_states, self._dof_state, self._rigid_body_state, self._contact_forces,
+                                                       self.dof_force_tensor, self._pd_target, force_sensor=self.vec_sensor_tensor,
+                                                       env_shape=self._dr.env_shape_device)
         pcfg = self.cfg.get("perturb", None)
         if pcfg:
             from ...perturb import make_schedule
@@ -808,6 +832,8 @@ class HumanoidIm:
             self._update_occl_training()
         if self._push is not None:   # (an env reset since the last step has progress 0: its push ends, a new pause is drawn)
             self._push.advance(self.progress_buf if self._push.capturable else self.progress_buf == 0)
+        if self._dr is not None:     # control delay and velocity push (phc_dr_advance); `self.actions` stays the undelayed tensor
+            self._dr.advance(self.actions.contiguous(), self.progress_buf)
 
     def _update_occl_training(self):
         """humanoid_im.py:1081-1092: occlusion spans of 30-59 steps start with probability occl_training_prob per tracked body and step (never the
@@ -827,6 +853,10 @@ class HumanoidIm:
             off, scale = self._torque_target_offset, self._torque_target_scale
         else:
             off, scale = self._pd_action_offset, self._pd_action_scale
+        if self._dr is not None:        # per-env physics: the K-block model, the delayed actions
+            L.check(self._lib.phc_sim_step_dr(self._dr.model_struct, self._sim_params, self._dr_sim_struct, self._dr.delayed_actions.data_ptr(), off.data_ptr(),
+                                              scale.data_ptr(), self._freeze_mask.data_ptr(), self.control_freq_inv, self._dr.sim_dr, _stream()), "phc_sim_step_dr")
+            return
         if self._push is not None:      # a schedule: the same launch in every step, its force buffer zero between pushes
             wrench = (self._push.force.data_ptr(), None, self.control_freq_inv)
         elif self._ext_pending is not None:   # one-shot wrench: this step only
@@ -852,6 +882,8 @@ class HumanoidIm:
         of mass, `torques` [N, NB, 3] in newton metres, env axes; either may be None.  They are copied into buffers of the task, act in the NEXT step() only -- over
         its first `sim_calls` simulate calls (the gym clears applied forces after one simulate()) -- and are then cleared.  They are no part of the published contact
         forces, force sensors or dof forces."""
+        if self._dr is not None:
+            raise NotImplementedError("apply_rigid_body_force_tensors on a task with domain_rand: the stepper has no launch with both")
         if self._push is not None:
             raise ValueError("apply_rigid_body_force_tensors on a task with a push schedule (+perturb.*): the two durations do not mix in one launch")
         self._check_wrench_supported("apply_rigid_body_force_tensors")
