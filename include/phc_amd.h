@@ -760,6 +760,41 @@ typedef struct {
 } phc_dr_args_t;
 int32_t phc_dr_advance(const phc_dr_args_t* args /* host */, void* stream);
 
+/* Clip processing on the device (csrc/phc_clip.hip, per-lane code csrc/phc_clip.h; an addition to ABI 37, which stays 37): `process_clip` of
+ * phc_amd/motion_lib.py for U concatenated clips of the SMPL family -- forward kinematics with the normalised local rotations, np.gradient and
+ * finite-difference angular velocities, the gaussian filter (sigma 2, radius 8, `nearest` clamped to each clip's own first and last frame), the joint
+ * velocities -- in fp64, rounded once to the fp32 records of phc_motion_lib_t (spherical layout, no extended bodies; pad floats written as 0).
+ * Two launches on `stream`, 256-thread blocks:
+ *   1. one lane per (frame, body) over tiles of up to 16 frames: the lane walks its own ancestor chain from the root; positions, both rotations and
+ *      the joint velocities go through an LDS image of the tile's records to coalesced stores; the fp64 positions and raw angular velocities go to
+ *      `scratch`, and one lane per frame records the frame's clip there;
+ *   2. one lane per velocity float of a record: the 17-tap filter over the scratch rows of the lane's clip.
+ * No lane loops over a clip's frames.  phc_clip_scratch_bytes(F, J) = 48 F J + 4 F rounded up to 8 (negative arguments: PHC_EINVAL).
+ * Before any device work, PHC_EINVAL for: a null args or pointer field, num_clips / num_bodies / num_trees < 1, num_frames < 2 num_clips,
+ * frame_stride != 20 num_bodies, scratch_bytes below phc_clip_scratch_bytes, an f64 / i64 array or the scratch not 8-byte aligned, an i32 / f32 array not
+ * 4-byte aligned; PHC_EUNSUPPORTED for num_bodies > PHC_MAX_BODIES and for a num_frames that does not fit the launch grids (6 num_bodies num_frames > (2^31 - 1) 256, or more than
+ * 2^31 - 1 tiles).
+ * The contents of the device arrays are the caller's duty (phc_amd/motion_lib.py validates them before the upload): clips of at least 2 frames,
+ * clip_start ascending from 0 to num_frames, clip_tree in [0, num_trees), parents[j] < j with exactly the entries < 0 as roots.  Whatever they hold, no
+ * lane reads or writes outside the arrays' stated sizes. */
+typedef struct {
+    int32_t num_clips, num_bodies, num_trees; /* U, J, trees */
+    int32_t frame_stride;                     /* floats per record: 20 J */
+    int64_t num_frames;                       /* F, all clips together */
+    const int32_t* parents;                   /* [J] */
+    const double*  local_translation;         /* [num_trees, J, 3] */
+    const int32_t* clip_tree;                 /* [U] */
+    const int64_t* clip_start;                /* [U + 1] frame offsets; the last entry is F */
+    const double*  clip_dt;                   /* [U] 1 / fps */
+    const double*  quat;                      /* [F, J, 4] global rotations, xyzw */
+    const double*  trans;                     /* [F, 3] root translation */
+    void*          scratch;                   /* phc_clip_scratch_bytes(F, J) bytes */
+    int64_t        scratch_bytes;
+    float*         frames;                    /* [F, frame_stride] out */
+} phc_clip_args_t;
+int64_t phc_clip_scratch_bytes(int64_t num_frames, int32_t num_bodies);
+int32_t phc_clip_process(const phc_clip_args_t* args /* host; all pointers device memory */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

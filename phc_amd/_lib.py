@@ -129,6 +129,12 @@ class DrArgs(C.Structure):
                 ("delayed_actions", c_p), ("root_states", c_p)]
 
 
+class ClipArgs(C.Structure):
+    _fields_ = [("num_clips", c_i32), ("num_bodies", c_i32), ("num_trees", c_i32), ("frame_stride", c_i32), ("num_frames", c_i64), ("parents", c_p),
+                ("local_translation", c_p), ("clip_tree", c_p), ("clip_start", c_p), ("clip_dt", c_p), ("quat", c_p), ("trans", c_p), ("scratch", c_p),
+                ("scratch_bytes", c_i64), ("frames", c_p)]
+
+
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
@@ -184,6 +190,8 @@ _OPTIONAL_SIGNATURES = {
     "phc_sim_force_generic": ([c_i32], c_i32),
     "phc_sim_step_dr": ([P(Model), P(SimParams), P(SimState), c_p, c_p, c_p, c_p, c_i32, P(SimDr), c_p], c_i32),
     "phc_dr_advance": ([P(DrArgs), c_p], c_i32),
+    "phc_clip_scratch_bytes": ([c_i64, c_i32], c_i64),
+    "phc_clip_process": ([P(ClipArgs), c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

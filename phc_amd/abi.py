@@ -146,6 +146,19 @@ def pack_frames(gts, grs, gvs, gavs, lrs, dvs, xp=np, gts_ext=None, grs_ext=None
     return out
 
 
+def clip_args_struct(num_clips, num_frames, num_bodies, num_trees, parents, local_translation, clip_tree, clip_start, clip_dt, quat, trans, scratch,
+                     scratch_bytes, frames, frame_stride=None):
+    """phc_clip_args_t (phc_clip_process): the arrays are torch tensors / numpy arrays or raw addresses (views into one staging buffer)."""
+    a = L.ClipArgs()
+    a.num_clips, a.num_bodies, a.num_trees, a.num_frames = int(num_clips), int(num_bodies), int(num_trees), int(num_frames)
+    a.frame_stride = frame_stride_for(int(num_bodies), 0, 3) if frame_stride is None else int(frame_stride)
+    addr = lambda x: x if x is None or isinstance(x, int) else ptr(x)
+    a.parents, a.local_translation, a.clip_tree, a.clip_start, a.clip_dt = (addr(x) for x in (parents, local_translation, clip_tree, clip_start, clip_dt))
+    a.quat, a.trans, a.scratch, a.frames = addr(quat), addr(trans), addr(scratch), addr(frames)
+    a.scratch_bytes = int(scratch_bytes)
+    return a
+
+
 def im_params_struct(dt, max_episode_length, reward_specs, power_reward, power_coefficient, enable_early_termination,
                      use_mean_termination, disable_collision_check, local_root_obs, root_height_obs, num_track_bodies,
                      track_slot, reset_mask, num_reset_bodies, first_reset_body, termination_distances, num_key_bodies, key_body_ids,

@@ -17,7 +17,9 @@ What is different inside (MI355X-first):
     (phc_amd/csrc/phc_kernels.hip) -- one lane per body;
   * clip loading (FK + finite-difference velocities, fp64 like poselib) is vectorised numpy over
     frames; the random heading is applied per env *after* the per-clip FK (rotation about z commutes
-    with FK, np.gradient and the gaussian filter), so a clip shared by many envs is processed once.
+    with FK, np.gradient and the gaussian filter), so a clip shared by many envs is processed once;
+    `clip_processing: device` runs the same per-clip arithmetic as two fp64 HIP launches instead
+    (`process_clips_device`, phc_amd/csrc/phc_clip.hip; SMPL family, opt-in).
 """
 import os
 from enum import Enum
@@ -327,11 +329,171 @@ def _run_clip_chunk(args):
     return [_run_clip_job(p, consts) for p in payloads]
 
 
+# ---- clip processing on the device (load_motions pass 2 with `clip_processing: device`) ------------------------------------------------------------------------------
+# phc_clip_process (csrc/phc_clip.hip) is `process_clip` + the fp32 packing for concatenated clips of the SMPL family.  The host's part is the upload: the crops go
+# as fp64 through a pinned staging buffer (two slots, so that filling one overlaps the copy of the other) into one device input buffer; whole clips are grouped into
+# chunks of at most `chunk_frames` frames, which bounds staging, input and scratch (24 bodies, 262 144 frames: 208 MB per staging slot, 208 MB input, 303 MB scratch)
+# whatever the draw.  The buffers are kept per device and re-used by later calls.
+CLIP_PROCESSING = ("host", "device")
+_CLIP_STAGE = {}
+CLIP_TIMING = None   # scripts/clip_load_time.py puts a list here: per chunk the HIP events (upload begins, upload done, launches done)
+
+
+def _clip_processing_of(cfg):
+    mode = cfg.get("clip_processing", "host")
+    if mode not in CLIP_PROCESSING:
+        raise ValueError(f"clip_processing must be one of {CLIP_PROCESSING}, not {mode!r}")
+    return mode
+
+
+def validate_clip_inputs(parents, local_translations, clip_tree, quats, trans, fps):
+    """What phc_clip_process leaves to its caller (the kernels cannot report it): -> (parents i32 [J], local translations f64 [trees, J, 3], clip_tree i32 [U],
+    frames per clip i64 [U], dt f64 [U]); ValueError otherwise."""
+    par = np.ascontiguousarray(np.asarray(parents), dtype=np.int32)
+    lt = np.ascontiguousarray(np.asarray(local_translations), dtype=np.float64)
+    J = par.shape[0]
+    if par.ndim != 1 or J < 1 or J > abi.MAX_BODIES:
+        raise ValueError(f"clip processing on the device takes 1 .. {abi.MAX_BODIES} bodies, not {par.shape}")
+    if lt.ndim != 3 or lt.shape[0] < 1 or lt.shape[1:] != (J, 3):
+        raise ValueError(f"local_translations must be [trees, {J}, 3], not {lt.shape}")
+    if par[0] >= 0 or any(par[j] >= j for j in range(J)):
+        raise ValueError("body 0 must be a root and every parent must precede its child")
+    tree = np.ascontiguousarray(np.asarray(clip_tree), dtype=np.int32)
+    U = len(quats)
+    if U < 1 or tree.shape != (U,) or len(trans) != U or len(fps) != U:
+        raise ValueError("one tree index, rotation track, translation track and fps per clip (at least one clip)")
+    if tree.min() < 0 or tree.max() >= lt.shape[0]:
+        raise ValueError(f"clip_tree must index the {lt.shape[0]} trees")
+    nf = np.zeros(U, dtype=np.int64)
+    for u, (q, t) in enumerate(zip(quats, trans)):
+        if q.ndim != 3 or q.shape[1:] != (J, 4) or t.shape != (q.shape[0], 3):
+            raise ValueError(f"clip {u}: rotations {q.shape} / translations {t.shape} are not [T, {J}, 4] / [T, 3]")
+        if q.shape[0] < 2:
+            raise ValueError(f"clip {u} has {q.shape[0]} frame(s): the finite differences need at least 2")
+        nf[u] = q.shape[0]
+    f = np.asarray(fps, dtype=np.float64)
+    if not (np.isfinite(f).all() and (f > 0).all()):
+        raise ValueError("fps must be positive")
+    return par, lt, tree, nf, 1.0 / f
+
+
+def _clip_chunks(nf, chunk_frames):
+    """Whole clips in runs of at most `chunk_frames` frames (a longer clip is a run of its own): [(first clip, end clip)]."""
+    out, u0, n = [], 0, 0
+    for u, t in enumerate(nf):
+        if u > u0 and n + int(t) > chunk_frames:
+            out.append((u0, u))
+            u0, n = u, 0
+        n += int(t)
+    out.append((u0, len(nf)))
+    return out
+
+
+class _ClipStage:
+    """One device's buffers: two pinned staging slots (each with the event of its last copy), the device input, the scratch."""
+
+    def __init__(self, device):
+        self.device = device
+        self.slots = [None, None]
+        self.events = [None, None]
+        self.turn = 0
+        self.stream = None
+        self.dev_in = None
+        self.scratch = None
+        self.uses = 0
+
+    @staticmethod
+    def _grown(buf, nbytes, **kw):
+        return buf if buf is not None and buf.numel() >= nbytes else torch.empty(nbytes, dtype=torch.uint8, **kw)
+
+    def slot(self, nbytes):
+        k = self.turn
+        self.turn ^= 1
+        if self.events[k] is not None:
+            self.events[k].synchronize()   # the copy out of this slot has finished: it may be overwritten
+        self.slots[k] = self._grown(self.slots[k], nbytes, pin_memory=True)
+        return k, self.slots[k]
+
+    def device_buffers(self, in_bytes, scratch_bytes):
+        self.dev_in = self._grown(self.dev_in, in_bytes, device=self.device)
+        self.scratch = self._grown(self.scratch, scratch_bytes, device=self.device)
+        return self.dev_in, self.scratch
+
+
+def process_clips_device(parents, local_translations, clip_tree, quats, trans, fps, device, chunk_frames=262144):
+    """The device counterpart of `_run_clip_job` per clip + concatenation: the packed fp32 frame records [F, stride] of all clips as ONE device tensor, computed by
+    phc_clip_process on torch's current stream.  parents [J]; local_translations [trees, J, 3]; clip_tree [U] the tree of each clip; quats / trans: U arrays
+    [T, J, 4] (xyzw, global) / [T, 3]; fps: U numbers.  No CPU fallback: a device that is not a HIP device is an error."""
+    quats = [np.asarray(q) for q in quats]
+    trans = [t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in trans]
+    par, lt, tree, nf, dt = validate_clip_inputs(parents, local_translations, clip_tree, quats, trans, fps)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"clip_processing=device runs on the HIP device only (no CPU fallback), not on {device}; use clip_processing=host")
+    lib = L.load()
+    if not hasattr(lib, "phc_clip_process"):
+        raise RuntimeError("this build of libphc_amd.so has no phc_clip_process; use clip_processing=host")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    J, F_ = par.shape[0], int(nf.sum())
+    stride = abi.frame_stride_for(J, 0, 3)
+    stage = _CLIP_STAGE.setdefault(device, _ClipStage(device))
+    stage.uses += 1
+    first = np.concatenate([[0], np.cumsum(nf)])
+    chunks = _clip_chunks(nf, int(chunk_frames))
+
+    def layout(u0, u1):
+        # one buffer: quat [fc, J, 4] f64 | trans [fc, 3] f64 | local_translation f64 | clip_dt [n] f64 | clip_start [n + 1] i64 | parents [J] i32 | clip_tree [n] i32
+        n, fc = u1 - u0, int(first[u1] - first[u0])
+        sizes = (fc * J * 32, fc * 24, lt.size * 8, n * 8, (n + 1) * 8, J * 4, n * 4)
+        return n, fc, sizes, [int(o) for o in np.concatenate([[0], np.cumsum([(s + 63) // 64 * 64 for s in sizes])])]
+
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream()
+        if stage.stream is not None and stage.stream != stream:
+            stage.stream.synchronize()   # (the buffers' last user ran on another stream)
+        stage.stream = stream
+        frames = torch.empty((F_, stride), dtype=torch.float32, device=device)
+        # sized once for the call's largest chunk: no buffer is replaced while an earlier chunk's launches may still read it
+        dev_in, scratch = stage.device_buffers(max(layout(*c)[3][-1] for c in chunks),
+                                               max(int(lib.phc_clip_scratch_bytes(int(first[u1] - first[u0]), J)) for u0, u1 in chunks))
+        for u0, u1 in chunks:
+            n, fc, sizes, offs = layout(u0, u1)
+            k, host = stage.slot(offs[-1])
+            hv = host.numpy()
+            view = lambda i, dtype, shape: hv[offs[i]:offs[i] + sizes[i]].view(dtype).reshape(shape)
+            np.concatenate(quats[u0:u1], axis=0, out=view(0, np.float64, (fc, J, 4)), casting="same_kind")
+            np.concatenate(trans[u0:u1], axis=0, out=view(1, np.float64, (fc, 3)), casting="same_kind")
+            view(2, np.float64, lt.shape)[...] = lt
+            view(3, np.float64, (n,))[...] = dt[u0:u1]
+            view(4, np.int64, (n + 1,))[...] = first[u0:u1 + 1] - first[u0]
+            view(5, np.int32, (J,))[...] = par
+            view(6, np.int32, (n,))[...] = tree[u0:u1]
+            timing = None if CLIP_TIMING is None else [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            if timing:
+                timing[0].record(stream)
+            dev_in[:offs[-1]].copy_(host[:offs[-1]], non_blocking=True)
+            if stage.events[k] is None:
+                stage.events[k] = torch.cuda.Event()
+            stage.events[k].record(stream)
+            if timing:
+                timing[1].record(stream)
+            base = dev_in.data_ptr()
+            args = abi.clip_args_struct(n, fc, J, lt.shape[0], base + offs[5], base + offs[2], base + offs[6], base + offs[4], base + offs[3], base + offs[0],
+                                        base + offs[1], scratch, int(lib.phc_clip_scratch_bytes(fc, J)), frames[int(first[u0]):int(first[u1])], stride)
+            L.check(lib.phc_clip_process(args, stream.cuda_stream), "phc_clip_process")
+            if timing:
+                timing[2].record(stream)
+                CLIP_TIMING.append(timing)
+    return frames
+
+
 class MotionLibBase:
     """See module docstring.  Mirrors reference MotionLibBase (motion_lib_base.py:114-567)."""
 
     def __init__(self, motion_lib_cfg):
         self.m_cfg = motion_lib_cfg
+        _clip_processing_of(self.m_cfg)
         self._sim_fps = 1 / self.m_cfg.get("step_dt", 1 / 30)
         self._device = torch.device(self.m_cfg.device)
         self.mesh_parsers = None
@@ -423,7 +585,12 @@ class MotionLibBase:
         consts = self._clip_consts(trees)
         jobs = [self._clip_payload(self._motion_data_list[u], t, max_len, crop[u]) for u, t in uniq]
         workers = int(self.m_cfg.get("num_workers", 0)) or default_pool_workers()
-        if len(jobs) >= int(self.m_cfg.get("pool_min_jobs", 256)) and workers > 1:
+        uniq_frames = None
+        if _clip_processing_of(self.m_cfg) == "device":
+            # `clip_processing: device` -- the same pairs through phc_clip_process: the records are born on the device, no worker pool is started
+            uniq_frames = self._process_clips_device(trees, jobs)
+            done = [(None, j[3], j[1].shape[0]) for j in jobs]
+        elif len(jobs) >= int(self.m_cfg.get("pool_min_jobs", 256)) and workers > 1:
             # chunks of jobs, each carrying the (small) constants: no per-worker state to set up or to go stale between calls
             per = max(1, -(-len(jobs) // (workers * 8)))
             chunks = [(consts, jobs[i:i + per]) for i in range(0, len(jobs), per)]
@@ -438,10 +605,10 @@ class MotionLibBase:
         # clip copy per env, motion_lib_base.py:300-307) are a device-side gather, and the per-env heading a device-side rotation
         dev = self._device
         self.num_bodies = self.num_joints
-        packed = [rec for rec, _, _ in done]
-        u_nf = np.array([p.shape[0] for p in packed], dtype=np.int64)
+        u_nf = np.array([n for _, _, n in done], dtype=np.int64)
         u_start = np.concatenate([[0], np.cumsum(u_nf)[:-1]])
-        uniq_frames = torch.from_numpy(np.concatenate(packed, axis=0)).to(dev)
+        if uniq_frames is None:
+            uniq_frames = torch.from_numpy(np.concatenate([rec for rec, _, _ in done], axis=0)).to(dev)
         e_slot = np.array([slot[(int(u), tree_of[e])] for e, u in enumerate(idx_np)], dtype=np.int64)
         nfs = [int(u_nf[k]) for k in e_slot]
         fpss = [done[k][1] for k in e_slot]
@@ -493,6 +660,14 @@ class MotionLibBase:
     def _clip_consts(self, trees):
         """Per-family constants of the clip workers (picklable, numpy only; no motion data)."""
         return {"kind": "smpl", "trees": [(np.asarray(t.parent_indices), np.asarray(t.local_translation)) for t in trees]}
+
+    def _process_clips_device(self, trees, jobs):
+        """Pass 2 on the device: the jobs' crops through `process_clips_device` -> [sum of frames, stride] on the library's device."""
+        consts = self._clip_consts(trees)["trees"]
+        if any(not np.array_equal(p, consts[0][0]) for p, _ in consts):
+            raise ValueError("clip_processing=device needs one topology for all skeleton trees")
+        return process_clips_device(consts[0][0], np.stack([lt for _, lt in consts]), [j[0] for j in jobs], [j[1] for j in jobs], [j[2] for j in jobs],
+                                    [j[3] for j in jobs], self._device, chunk_frames=int(self.m_cfg.get("clip_chunk_frames", 262144)))
 
     def _clip_payload(self, clip, tree_index, max_len, start):
         """One job of the clip workers: the crop of the clip's arrays (motion_lib_smpl.py:101-180 up to, not including, the per-env heading)."""
@@ -683,6 +858,8 @@ class MotionLibReal(MotionLibBase):
     dofs_per_joint = 1
 
     def __init__(self, motion_lib_cfg):
+        if _clip_processing_of(motion_lib_cfg) == "device":
+            raise NotImplementedError("clip_processing=device covers the SMPL family; the robots' matrix FK and extended bodies run with clip_processing=host")
         self.robot_model = motion_lib_cfg["robot_model"]
         ext = list(motion_lib_cfg["robot"].get("extend_config", []))
         names = self.robot_model.body_names
