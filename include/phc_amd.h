@@ -795,6 +795,87 @@ typedef struct {
 int64_t phc_clip_scratch_bytes(int64_t num_frames, int32_t num_bodies);
 int32_t phc_clip_process(const phc_clip_args_t* args /* host; all pointers device memory */, void* stream);
 
+/* HumanoidTeleop's regularisation rewards and its recovery window after a velocity push (csrc/phc_teleop.hip, per-env code csrc/phc_teleop.h; an addition to
+ * ABI 37, which stays 37; reference: phc/env/tasks/humanoid_teleop.py:95-101,167-307).  One launch per env step AFTER phc_im_post_physics on the same stream;
+ * a group of 32 lanes per env, lanes along a DoF row, 256-thread blocks; every sum is a fixed-order butterfly over the group (no atomics): the same inputs
+ * give the same bits at any num_envs.  Per env i, with R = popcount(term_mask) and C = num_im_cols:
+ *   (a) the terms of term_mask (bit PHC_TELEOP_*), tau = dof_force, (q, qd) = dof_state, a = actions, F = contact_force and v, rot = rigid_body_state of the
+ *       bodies feet[0 .. num_feet):
+ *         DOF_POS_LIMITS  sum_d max(lo_d - q_d, 0) + max(q_d - hi_d, 0)          TORQUE_LIMITS  sum_d max(|tau_d| - torque_limits_d, 0)
+ *         TORQUES         sum_d tau_d^2                                          DOF_VEL        sum_d qd_d^2
+ *         DOF_ACC         sum_d ((last_dof_vel_d - qd_d) / dt)^2                 ACTION_RATE    sum_d (last_actions_d - a_d)^2
+ *         SLIPPAGE        sum_f |v_f| [|F_f| > 1]                                FEET_CONTACT_FORCES  sum_f max(|F_f| - max_contact_force, 0)
+ *         STUMBLE         1 if any_f |F_f,xy| > 5 |F_f,z| else 0
+ *         FEET_AIR_TIME   contact_f = F_f,z > 1; filt_f = contact_f or last_contacts_f; last_contacts_f = contact_f; first_f = feet_air_time_f > 0 and filt_f;
+ *                         feet_air_time_f += dt; value = sum_f (feet_air_time_f - 0.25) first_f; feet_air_time_f = 0 where filt_f; value *= [|ref root v_xy| > 0.1],
+ *                         the reference root velocity looked up in `lib` at the imitation reward's own time: progress_buf[i] (+ 1 where recovery_counter[i] > 0:
+ *                         phc_im_post_physics held the progress of a gated env) x dt + motion_start_times[i] + motion_start_times_offset[i];
+ *         FEET_ORI        |g_xy| of foot 0 + |g_xy| of foot 1, g = (0, 0, -1) rotated into the foot's frame;
+ *   (b) column r of the new ones is the term order[r] times scale[order[r]] (the caller's reward_specs value x dt); rew_buf[i] += the columns in their order;
+ *       reward_raw[i] = reward_im[i, 0 .. C) followed by the R columns (phc_im_post_physics writes its own C columns with a row stride of C: reward_im is
+ *       that tensor, reward_raw the public [N, C + R] one);
+ *   (c) last_actions[i] = actions[i], last_dof_vel[i] = qd (each where the pointer is given); feet_air_time / last_contacts as under FEET_AIR_TIME.  None of
+ *       them is cleared by an env reset (the reference does not clear them either);
+ *   (d) push_interval > 0: with k = dr_k[i] (phc_dr_advance has already counted this step), where k > 0 and k % push_interval == 0 -- phc_dr_advance pushes the
+ *       env at the START of the next step -- recovery_counter[i] = recovery_steps + 1: phc_im_post_physics decrements first and gates while the result is
+ *       positive, so the env is neither reset nor advanced for recovery_steps steps from the pushed one on.  An env reset in between is not pushed and its
+ *       counter is zeroed by the reset launch.
+ * A term that is off reads none of its inputs: every input below is nullable unless a term of the mask (or a state array that is given) needs it.
+ * PHC_EINVAL before any device work: a null args / rew_buf / reward_raw; reward_im null with num_im_cols > 0; a null input that a term of the mask or a given
+ * state array needs (dof_state: DOF_POS_LIMITS, DOF_VEL, DOF_ACC, last_dof_vel; dof_limits_lower / upper: DOF_POS_LIMITS; dof_force: TORQUE_LIMITS, TORQUES;
+ * torque_limits: TORQUE_LIMITS; last_dof_vel: DOF_ACC; actions: ACTION_RATE, last_actions; last_actions: ACTION_RATE; contact_force: SLIPPAGE,
+ * FEET_CONTACT_FORCES, STUMBLE, FEET_AIR_TIME; rigid_body_state: SLIPPAGE, FEET_ORI; feet_air_time, last_contacts, progress_buf, motion_start_times,
+ * motion_start_times_offset: FEET_AIR_TIME; dr_k, recovery_counter: push_interval > 0); num_envs < 0, num_dof < 1, num_feet outside [0, PHC_TELEOP_MAX_FEET],
+ * num_bodies outside [1, PHC_MAX_BODIES] or a foot outside [0, num_bodies) when num_feet > 0, num_im_cols outside [0, 8], FEET_ORI with fewer than two feet,
+ * FEET_AIR_TIME without a motion library (lib null, or without frames or clip tables), a term_mask with bits at or above
+ * PHC_TELEOP_NUM_TERMS, an `order` that is not the mask's terms each once, dt not positive and finite, push_interval < 0 or recovery_steps < 0.
+ * PHC_EUNSUPPORTED: (none).  num_envs == 0 returns 0 without a launch. */
+#define PHC_TELEOP_DOF_POS_LIMITS 0
+#define PHC_TELEOP_TORQUE_LIMITS 1
+#define PHC_TELEOP_TORQUES 2
+#define PHC_TELEOP_DOF_VEL 3
+#define PHC_TELEOP_DOF_ACC 4
+#define PHC_TELEOP_ACTION_RATE 5
+#define PHC_TELEOP_SLIPPAGE 6
+#define PHC_TELEOP_FEET_CONTACT_FORCES 7
+#define PHC_TELEOP_STUMBLE 8
+#define PHC_TELEOP_FEET_AIR_TIME 9
+#define PHC_TELEOP_FEET_ORI 10
+#define PHC_TELEOP_NUM_TERMS 11
+#define PHC_TELEOP_MAX_FEET 8
+typedef struct {
+    int32_t num_envs, num_dof, num_bodies, num_feet;
+    int32_t num_im_cols;                          /* C: the columns phc_im_post_physics wrote (4, or 5 with the power reward) */
+    uint32_t term_mask;                           /* bit t = term t is on */
+    int32_t order[PHC_TELEOP_NUM_TERMS];          /* order[r] = the term of new column r, r < popcount(term_mask) */
+    float   scale[PHC_TELEOP_NUM_TERMS];          /* by term: reward_specs value x dt */
+    int32_t feet[PHC_TELEOP_MAX_FEET];            /* body indices, the config's order */
+    float   dt, max_contact_force;
+    int32_t push_interval, recovery_steps;        /* env steps; push_interval 0 = no recovery window */
+    const float* dof_state;                       /* [N, D, 2] position, velocity */
+    const float* dof_limits_lower;                /* [D] */
+    const float* dof_limits_upper;                /* [D] */
+    const float* torque_limits;                   /* [D] */
+    const float* dof_force;                       /* [N, D] */
+    const float* actions;                         /* [N, D] the policy's action, not the delayed one */
+    const float* contact_force;                   /* [N, NB, 3] */
+    const float* rigid_body_state;                /* [N, NB, 13] */
+    const int64_t* progress_buf;                  /* [N] as phc_im_post_physics left it */
+    const float* motion_start_times;              /* [N] */
+    const float* motion_start_times_offset;       /* [N] */
+    const int64_t* sampled_motion_ids;            /* [N]; nullable = env i plays clip i */
+    const int32_t* dr_k;                          /* [N] phc_dr_args_t.k after this step's phc_dr_advance */
+    int32_t* recovery_counter;                    /* [N] phc_im_buffers_t.recovery_counter */
+    float*   last_actions;                        /* [N, D] state */
+    float*   last_dof_vel;                        /* [N, D] state */
+    float*   feet_air_time;                       /* [N, num_feet] state */
+    uint8_t* last_contacts;                       /* [N, num_feet] state, 0 / 1 */
+    float*   rew_buf;                             /* [N] in / out */
+    const float* reward_im;                       /* [N, C] */
+    float*   reward_raw;                          /* [N, C + R] out */
+} phc_teleop_args_t;
+int32_t phc_teleop_rewards(const phc_motion_lib_t* lib /* host; nullable without FEET_AIR_TIME */, const phc_teleop_args_t* args /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

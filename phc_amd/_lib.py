@@ -135,6 +135,21 @@ class ClipArgs(C.Structure):
                 ("scratch_bytes", c_i64), ("frames", c_p)]
 
 
+TELEOP_TERMS = ("dof_pos_limits", "torque_limits", "torques", "dof_vel", "dof_acc", "action_rate", "slippage", "feet_contact_forces", "stumble",
+                "feet_air_time_teleop", "feet_ori")   # PHC_TELEOP_*: the bit of each term
+TELEOP_MAX_FEET = 8   # PHC_TELEOP_MAX_FEET
+
+
+class TeleopArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_dof", c_i32), ("num_bodies", c_i32), ("num_feet", c_i32), ("num_im_cols", c_i32), ("term_mask", C.c_uint32),
+                ("order", c_i32 * len(TELEOP_TERMS)), ("scale", c_f * len(TELEOP_TERMS)), ("feet", c_i32 * TELEOP_MAX_FEET), ("dt", c_f),
+                ("max_contact_force", c_f), ("push_interval", c_i32), ("recovery_steps", c_i32), ("dof_state", c_p), ("dof_limits_lower", c_p),
+                ("dof_limits_upper", c_p), ("torque_limits", c_p), ("dof_force", c_p), ("actions", c_p), ("contact_force", c_p), ("rigid_body_state", c_p),
+                ("progress_buf", c_p), ("motion_start_times", c_p), ("motion_start_times_offset", c_p), ("sampled_motion_ids", c_p), ("dr_k", c_p),
+                ("recovery_counter", c_p), ("last_actions", c_p), ("last_dof_vel", c_p), ("feet_air_time", c_p), ("last_contacts", c_p), ("rew_buf", c_p),
+                ("reward_im", c_p), ("reward_raw", c_p)]
+
+
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
@@ -192,6 +207,7 @@ _OPTIONAL_SIGNATURES = {
     "phc_dr_advance": ([P(DrArgs), c_p], c_i32),
     "phc_clip_scratch_bytes": ([c_i64, c_i32], c_i64),
     "phc_clip_process": ([P(ClipArgs), c_p], c_i32),
+    "phc_teleop_rewards": ([P(MotionLib), P(TeleopArgs), c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

@@ -265,3 +265,31 @@ def task_index_tables(model, track_bodies, reset_bodies, key_bodies, amp_remove_
             amp_slot[j] = s
             s += 1
     return track_slot, reset_mask, key_ids, amp_slot, s
+
+
+def teleop_args_struct(num_envs, num_dof, rew_buf, reward_raw, reward_im=None, terms=(), scales=None, dt=1 / 30, num_bodies=0, feet=(), max_contact_force=0.0,
+                       push_interval=0, recovery_steps=60, **arrays):
+    """phc_teleop_args_t (phc_teleop_rewards).  `terms`: names of _lib.TELEOP_TERMS in column order; `scales`: {name: reward_specs value x dt}; `arrays`: the
+    nullable inputs and state arrays by field name (torch tensors / numpy arrays; what a term that is off would read may stay out)."""
+    a = L.TeleopArgs()
+    a.num_envs, a.num_dof, a.num_bodies, a.num_feet = int(num_envs), int(num_dof), int(num_bodies), len(feet)
+    assert len(feet) <= L.TELEOP_MAX_FEET, "at most PHC_TELEOP_MAX_FEET feet"
+    for i, b in enumerate(feet):
+        a.feet[i] = int(b)
+    a.num_im_cols = 0 if reward_im is None else int(reward_im.shape[1])
+    mask = 0
+    for r, name in enumerate(terms):
+        t = L.TELEOP_TERMS.index(name)
+        mask |= 1 << t
+        a.order[r] = t
+        a.scale[t] = float(np.float32((scales or {}).get(name, 1.0)))
+    a.term_mask = mask
+    a.dt, a.max_contact_force = float(np.float32(dt)), float(np.float32(max_contact_force))
+    a.push_interval, a.recovery_steps = int(push_interval), int(recovery_steps)
+    a.rew_buf, a.reward_raw, a.reward_im = ptr(rew_buf), ptr(reward_raw), ptr(reward_im)
+    known = {n for n, _ in L.TeleopArgs._fields_}
+    for name, x in arrays.items():
+        if name not in known:
+            raise TypeError(f"phc_teleop_args_t has no field {name!r}")
+        setattr(a, name, ptr(x))
+    return a

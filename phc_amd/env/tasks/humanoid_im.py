@@ -68,6 +68,8 @@ class HumanoidIm:
 
     # device-built list of the envs that finished in the last step (phc_im_buffers_t.reset_list): reset_done() works on it
     _use_reset_list = True
+    # hook of post_physics_step between the post-physics launch and the host bookkeeping: a method that issues launches only (the step stays capturable)
+    _post_physics_launch = None
 
     # ------------------------------------------------------------------ construction
     def __init__(self, cfg, sim_params=None, physics_engine=None, device_type="cuda", device_id=0, headless=True):
@@ -919,6 +921,8 @@ class HumanoidIm:
         buf = self._buffers(amp_in, amp_out)
         L.check(self._lib.phc_im_post_physics(self._model_struct, self._motion_lib.struct, self._im_params, self._sim_struct, buf,
                                               _stream()), "phc_im_post_physics")
+        if self._post_physics_launch is not None:   # a subclass's launch behind the post-physics one, on its stream (HumanoidTeleop: phc_teleop_rewards)
+            self._post_physics_launch()
         self._obs_noise()
         self._post_physics_host(new_head)
         if self._eval_acc is not None:   # evaluation sweep with eval_metrics=device: one launch instead of the lookup, the copies and the host metrics
