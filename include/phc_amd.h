@@ -876,6 +876,63 @@ typedef struct {
 } phc_teleop_args_t;
 int32_t phc_teleop_rewards(const phc_motion_lib_t* lib /* host; nullable without FEET_AIR_TIME */, const phc_teleop_args_t* args /* host */, void* stream);
 
+/* Tracking of streamed keypoints: the per-step work of HumanoidImDemo / HumanoidImMCPDemo (csrc/phc_stream.hip, per-lane code csrc/phc_stream.h; an addition
+ * to ABI 37, which stays 37; reference: phc/env/tasks/humanoid_im_mcp_demo.py:252-321).  One launch per env step AFTER phc_im_post_physics on the same stream
+ * (mode PHC_STREAM_ADVANCE) and one after every reset launch (mode PHC_STREAM_OBSERVE); a group of 32 lanes per env, lanes along the bodies (bodies l, l + 32),
+ * 256-thread blocks, no LDS, no atomics; sums over the group are phc_group.h's fixed-order butterfly: the same inputs give the same bits at any num_envs.
+ * ADVANCE, per env i with W = window, the env's ring of W past samples, L = min(count[i] + 1, W):
+ *   (1) p_j = frames[r, perm[j]] for body j (r = i, or 0 when frame_rows == 1; perm null = identity); q_j = p_j - p_0;
+ *   (2) limb_scale: s = mean over the pairs k < num_pairs of |q_parent_k - q_child_k| / pair_length[k] (fp32, fixed order); q_j /= s;
+ *   (3) q -> ring_body[i, head[i]], p_0 -> ring_root[i, head[i]]; head[i] = (head[i] + 1) % W; count[i] = L;
+ *   (4) with the L samples oldest first x_0 .. x_{L-1}: Q_j = sum_k fold[3][L-1][k] q_j,k and T_c = sum_k fold[c][L-1][k] p_0,k,c for the axes c = 0, 1, 2
+ *       (fold[s][L-1][k]: fp64 [4, fold_window, fold_window]; the value AT THE NEWEST SAMPLE of a gaussian filter with mirrored ends over L samples; rows
+ *       0..2 the root translation's axes, row 3 the bodies; the caller builds it, phc_amd/stream.py);
+ *   (5) ref_j = frame_mat (Q_j + T) (row-major 3 x 3, i.e. (Q + T) @ M^T); vel_j = (ref_j - cur_ref[i, j]) / dt where has_prev[i], else 0; has_prev[i] = 1;
+ *       sums and the difference in fp64, rounded once; cur_ref[i, j] = ref_j, cur_vel[i, j] = vel_j.
+ * OBSERVE skips (1) - (5): ref = cur_ref, vel = cur_vel; rings, head, count and has_prev are not touched.
+ * Both modes then, for the tracked bodies (prm->track_slot): with d = |root body pos - ref of the body in track slot 0 (track_root_body)| and where
+ * prm->zero_out_far: d > close_distance: targets of the slots >= 1 := the body's own position, every target velocity := the body's; d > far_distance: the
+ * slot-0 target := body + (ref - body) / d x far_distance (humanoid_im_mcp_demo.py:296-306; the distances are this struct's, not prm's); the obs_v 7 task
+ * observation of that target into obs_buf[i, num_self_obs ..) (root rotation with prm->remove_base_rot); reset_buf[i] = terminate_buf[i] = 0 (where given);
+ * track_err[i] = mean over the tracked bodies of |body pos - ref| (the ungated ref).
+ * PHC_EINVAL before any device work: a null model / prm / args / prm->track_slot / cur_ref / cur_vel / rigid_body_state / obs_buf / track_err; num_envs < 0;
+ * model->num_bodies outside [1, PHC_MAX_BODIES]; prm->num_track_bodies outside [1, num_bodies]; track_root_body outside [0, num_bodies); a mode other than the two;
+ * in ADVANCE: window outside [1, PHC_STREAM_MAX_WINDOW], fold_window < window, a null frames / fold / ring_body / ring_root / head / count / has_prev,
+ * frame_rows other than 1 or num_envs, num_pairs outside [0, PHC_STREAM_MAX_PAIRS] (limb_scale: outside [1, ..]), a pair index outside [0, num_bodies), a
+ * pair_length or dt that is not positive and finite.  PHC_EUNSUPPORTED: prm->obs_v other than 7, prm->num_traj_samples > 1.  num_envs == 0 returns 0 without
+ * a launch. */
+#define PHC_STREAM_ADVANCE 0
+#define PHC_STREAM_OBSERVE 1
+#define PHC_STREAM_MAX_WINDOW 64
+#define PHC_STREAM_MAX_PAIRS 8
+typedef struct {
+    int32_t num_envs, mode;
+    int32_t window, fold_window;                  /* W; the side of the fold table (>= W) */
+    int32_t frame_rows;                           /* 1: one staged frame for all envs; else num_envs */
+    int32_t limb_scale, num_pairs;
+    int32_t pair_parent[PHC_STREAM_MAX_PAIRS], pair_child[PHC_STREAM_MAX_PAIRS];   /* body indices (after perm) */
+    float   pair_length[PHC_STREAM_MAX_PAIRS];
+    float   frame_mat[9];                         /* row-major M: ref = M x */
+    float   dt, close_distance, far_distance;
+    int32_t track_root_body;                      /* the body in track slot 0 */
+    const float*   frames;                        /* [frame_rows, NB, 3] staged keypoints, the source's joint order */
+    const int32_t* perm;                          /* [NB] body j reads joint perm[j]; nullable = identity */
+    const double*  fold;                          /* [4, fold_window, fold_window] */
+    float*   ring_body;                           /* [N, W, NB, 3] state */
+    float*   ring_root;                           /* [N, W, 3] state */
+    int32_t* head;                                /* [N] state: the slot the next sample takes */
+    int32_t* count;                               /* [N] state: samples held, <= W */
+    uint8_t* has_prev;                            /* [N] state: cur_ref holds a previous frame */
+    float*   cur_ref;                             /* [N, NB, 3] state / out: the task's ref_body_pos */
+    float*   cur_vel;                             /* [N, NB, 3] out: the task's ref_body_vel */
+    const float* rigid_body_state;                /* [N, NB, 13] */
+    float*   obs_buf;                             /* [N, num_self_obs + num_task_obs]: the task block is written */
+    int64_t* reset_buf;                           /* [N] out, nullable */
+    int64_t* terminate_buf;                       /* [N] out, nullable */
+    float*   track_err;                           /* [N] out */
+} phc_stream_args_t;
+int32_t phc_stream_track(const phc_model_t* model /* host */, const phc_im_params_t* prm /* host */, const phc_stream_args_t* args /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,20 @@ class TeleopArgs(C.Structure):
                 ("reward_im", c_p), ("reward_raw", c_p)]
 
 
+STREAM_MAX_WINDOW = 64   # PHC_STREAM_MAX_WINDOW
+STREAM_MAX_PAIRS = 8     # PHC_STREAM_MAX_PAIRS
+STREAM_ADVANCE, STREAM_OBSERVE = 0, 1   # PHC_STREAM_*: phc_stream_args_t.mode
+
+
+class StreamArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("mode", c_i32), ("window", c_i32), ("fold_window", c_i32), ("frame_rows", c_i32), ("limb_scale", c_i32),
+                ("num_pairs", c_i32), ("pair_parent", c_i32 * STREAM_MAX_PAIRS), ("pair_child", c_i32 * STREAM_MAX_PAIRS),
+                ("pair_length", c_f * STREAM_MAX_PAIRS), ("frame_mat", c_f * 9), ("dt", c_f), ("close_distance", c_f), ("far_distance", c_f),
+                ("track_root_body", c_i32), ("frames", c_p), ("perm", c_p), ("fold", c_p), ("ring_body", c_p), ("ring_root", c_p), ("head", c_p),
+                ("count", c_p), ("has_prev", c_p), ("cur_ref", c_p), ("cur_vel", c_p), ("rigid_body_state", c_p), ("obs_buf", c_p), ("reset_buf", c_p),
+                ("terminate_buf", c_p), ("track_err", c_p)]
+
+
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
@@ -208,6 +222,7 @@ _OPTIONAL_SIGNATURES = {
     "phc_clip_scratch_bytes": ([c_i64, c_i32], c_i64),
     "phc_clip_process": ([P(ClipArgs), c_p], c_i32),
     "phc_teleop_rewards": ([P(MotionLib), P(TeleopArgs), c_p], c_i32),
+    "phc_stream_track": ([P(Model), P(ImParams), P(StreamArgs), c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

@@ -293,3 +293,29 @@ def teleop_args_struct(num_envs, num_dof, rew_buf, reward_raw, reward_im=None, t
             raise TypeError(f"phc_teleop_args_t has no field {name!r}")
         setattr(a, name, ptr(x))
     return a
+
+
+def stream_args_struct(num_envs, window, fold, frames, *, mode=L.STREAM_ADVANCE, limb_pairs=(), limb_lengths=(), limb_scale=False, frame_mat=None, dt=1 / 30,
+                       close_distance=0.25, far_distance=3.0, track_root_body=0, **arrays):
+    """phc_stream_args_t (phc_stream_track).  `fold`: the fp64 table [4, FW, FW] of phc_amd.stream.fold_table; `frames`: the staging buffer [1 or N, NB, 3];
+    `limb_pairs`: (parent, child) body indices; `frame_mat`: 3 x 3, row-major; `arrays`: the other pointer fields by name (torch tensors / numpy arrays)."""
+    a = L.StreamArgs()
+    a.num_envs, a.mode, a.window = int(num_envs), int(mode), int(window)
+    a.fold_window = 0 if fold is None else int(fold.shape[-1])
+    a.frame_rows = 0 if frames is None else int(frames.shape[0])
+    assert len(limb_pairs) <= L.STREAM_MAX_PAIRS and len(limb_pairs) == len(limb_lengths), "at most PHC_STREAM_MAX_PAIRS limb pairs, a length each"
+    a.limb_scale, a.num_pairs = int(bool(limb_scale)), len(limb_pairs)
+    for k, ((p, c), ln) in enumerate(zip(limb_pairs, limb_lengths)):
+        a.pair_parent[k], a.pair_child[k], a.pair_length[k] = int(p), int(c), float(np.float32(ln))
+    M = np.eye(3) if frame_mat is None else np.asarray(frame_mat, dtype=np.float64).reshape(3, 3)
+    for k, v in enumerate(M.reshape(-1)):
+        a.frame_mat[k] = float(np.float32(v))
+    a.dt, a.close_distance, a.far_distance = float(np.float32(dt)), float(np.float32(close_distance)), float(np.float32(far_distance))
+    a.track_root_body = int(track_root_body)
+    a.fold, a.frames = ptr(fold), ptr(frames)
+    known = {n for n, _ in L.StreamArgs._fields_}
+    for name, x in arrays.items():
+        if name not in known:
+            raise TypeError(f"phc_stream_args_t has no field {name!r}")
+        setattr(a, name, ptr(x))
+    return a

@@ -169,7 +169,8 @@ def parse_task(cfg, rl_device=None, device_id=None, headless=True):
     from .humanoid_im_mcp import HumanoidImMCP
     from .humanoid_im_mcp_getup import HumanoidImMCPGetup
     from .humanoid_teleop import HumanoidTeleop
-    for cls in (HumanoidIm, HumanoidImGetup, HumanoidImMCP, HumanoidImMCPGetup, HumanoidTeleop):
+    from .humanoid_im_demo import HumanoidImDemo, HumanoidImMCPDemo
+    for cls in (HumanoidIm, HumanoidImGetup, HumanoidImMCP, HumanoidImMCPGetup, HumanoidTeleop, HumanoidImDemo, HumanoidImMCPDemo):
         TASKS.setdefault(cls.__name__, cls)
     name = cfg["env"]["task"]
     if name not in TASKS:

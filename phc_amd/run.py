@@ -80,10 +80,14 @@ def play(agent, task, env, steps=300):
     rew_sum = torch.zeros(task.num_envs, device=task.device)
     ep_len = torch.zeros(task.num_envs, device=task.device)
     lens, rews = [], []
+    streams = hasattr(task, "set_keypoints")   # HumanoidImDemo / HumanoidImMCPDemo: the tracking error of the streamed keypoints, summed on the device
+    stream_err = torch.zeros((), device=task.device) if streams else None
     with torch.no_grad():
         for _ in range(steps):
             obs, r, done, info = env.step(agent.preprocess_actions(agent.get_action_values(obs)["mus"]))
             task.render()   # one frame per env step with `+render.video=DIR` (base_task.py:405-437); a no-op otherwise
+            if streams:
+                stream_err += task.extras["stream_err"].mean()
             rew_sum += r
             ep_len += 1
             ids = done.nonzero(as_tuple=False).flatten()
@@ -98,6 +102,8 @@ def play(agent, task, env, steps=300):
     out = {"episodes": int(lens.numel()), "mean_episode_length": float(lens.mean()), "mean_episode_reward": float(rews.mean()), "steps": steps}
     if getattr(task, "_push", None) is not None:   # `+perturb.*` (phc_amd/perturb.py): pushes started during the rollout, all envs
         out["perturb_pushes"] = int(task._push.pushes) - pushes0
+    if streams:
+        out["stream_err_mm"] = float(stream_err) / max(steps, 1) * 1000.0
     return out
 
 
