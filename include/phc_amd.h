@@ -933,6 +933,42 @@ typedef struct {
 } phc_stream_args_t;
 int32_t phc_stream_track(const phc_model_t* model /* host */, const phc_im_params_t* prm /* host */, const phc_stream_args_t* args /* host */, void* stream);
 
+/* ---- Distilling a composed controller into one MLP (csrc/phc_distill.hip; additive, ABI 37 unchanged) ------------------------------------------------------
+ * phc_dataset_record: the evaluation sweep's `collect_dataset` (im_amp_players.py:95-99,132-151), ONE launch per env step behind the post-physics launch.
+ * Env i with step < rows[i] stores, at row row_start[i] + step of the clip-major batch block, the observation it acted on (obs_prev[i]), clean_actions[i],
+ * actions[i] and reset_buf[i]; rows at or past `capacity` are never written.  Then obs_prev[i] = obs_buf[i] for EVERY env.  rows = max(num_steps - 1, 0) and
+ * row_start = its exclusive prefix sum give the layout of the reference's np.concatenate of the per-clip slices.
+ * PHC_EINVAL before any device work: a null args or pointer field, num_envs / obs_dim / num_actions / capacity < 1, step < 0. */
+typedef struct {
+    int32_t num_envs, obs_dim, num_actions, step;
+    int64_t capacity;                 /* R: rows of the batch block */
+    const float*   obs_buf;           /* [N, obs_dim] the task's observation after this step */
+    float*         obs_prev;          /* [N, obs_dim] state: the observation before this step */
+    const float*   clean_actions;     /* [N, A] */
+    const float*   actions;           /* [N, A] what the task received */
+    const int64_t* reset_buf;         /* [N] after the step */
+    const int64_t* rows;              /* [N] */
+    const int64_t* row_start;         /* [N] */
+    float*   obs;                     /* [R, obs_dim] out */
+    float*   clean;                   /* [R, A] out */
+    float*   env;                     /* [R, A] out */
+    int64_t* reset;                   /* [R] out */
+} phc_record_args_t;
+int32_t phc_dataset_record(const phc_record_args_t* args /* host */, void* stream);
+
+/* y = z / (1 + exp(-z)) on bf16 [rows, cols] (contiguous), evaluated in fp32, stored as bf16; finite for every finite z (-0 at the negative end). */
+int32_t phc_silu_bf16(const void* z, int64_t rows, int32_t cols, void* y, void* stream);
+/* gz = gy s (1 + z (1 - s)), s = sigmoid(z), stored as bf16 (gz must not alias gy / z), and the fp32 column sums of the unrounded products: the contract of
+ * phc_colsum_relu_bf16 (workspace phc_colsum_workspace(rows, cols); out == NULL runs the first stage only and leaves phc_colsum_chunks(rows) partials for
+ * phc_colsum_finish_batch; bit-reproducible). */
+int32_t phc_colsum_silu_bf16(const void* gy, const void* z, int64_t rows, int32_t cols, void* gz, float* out, float* workspace, void* stream);
+/* nn.MSELoss(): loss_out[0] = mean over batch x dim of (pred[r, d] - target[q, d])^2 with q = row_index[r] (NULL: q = r), grad = 2 (pred - target) / (batch dim)
+ * in pred's type (bf16 when is_bf16, else fp32); target fp32 [*, dim].  Sums in a fixed order (fp64 per-block partials, one finishing block): two runs give
+ * the same bits.  workspace: phc_mse_loss_workspace() bytes.  PHC_EINVAL: a null pred / target / grad / loss_out / workspace, batch or dim < 1. */
+int64_t phc_mse_loss_workspace(void);
+int32_t phc_mse_loss(const void* pred, int32_t is_bf16, const float* target, const int64_t* row_index, int64_t batch, int32_t dim, void* grad, float* loss_out,
+                     double* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,12 @@ class StreamArgs(C.Structure):
                 ("terminate_buf", c_p), ("track_err", c_p)]
 
 
+class RecordArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("obs_dim", c_i32), ("num_actions", c_i32), ("step", c_i32), ("capacity", c_i64), ("obs_buf", c_p), ("obs_prev", c_p),
+                ("clean_actions", c_p), ("actions", c_p), ("reset_buf", c_p), ("rows", c_p), ("row_start", c_p), ("obs", c_p), ("clean", c_p), ("env", c_p),
+                ("reset", c_p)]
+
+
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
@@ -223,6 +229,11 @@ _OPTIONAL_SIGNATURES = {
     "phc_clip_process": ([P(ClipArgs), c_p], c_i32),
     "phc_teleop_rewards": ([P(MotionLib), P(TeleopArgs), c_p], c_i32),
     "phc_stream_track": ([P(Model), P(ImParams), P(StreamArgs), c_p], c_i32),
+    "phc_dataset_record": ([P(RecordArgs), c_p], c_i32),
+    "phc_silu_bf16": ([c_p, c_i64, c_i32, c_p, c_p], c_i32),
+    "phc_colsum_silu_bf16": ([c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p], c_i32),
+    "phc_mse_loss_workspace": ([], c_i64),
+    "phc_mse_loss": ([c_p, c_i32, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

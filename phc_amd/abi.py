@@ -319,3 +319,15 @@ def stream_args_struct(num_envs, window, fold, frames, *, mode=L.STREAM_ADVANCE,
             raise TypeError(f"phc_stream_args_t has no field {name!r}")
         setattr(a, name, ptr(x))
     return a
+
+
+def record_args_struct(num_envs, obs_dim, num_actions, step, capacity, **arrays):
+    """phc_record_args_t (phc_dataset_record): `arrays` are the pointer fields by name (torch tensors / numpy arrays, contiguous)."""
+    a = L.RecordArgs()
+    a.num_envs, a.obs_dim, a.num_actions, a.step, a.capacity = int(num_envs), int(obs_dim), int(num_actions), int(step), int(capacity)
+    known = {n for n, _ in L.RecordArgs._fields_}
+    for name, x in arrays.items():
+        if name not in known:
+            raise TypeError(f"phc_record_args_t has no field {name!r}")
+        setattr(a, name, ptr(x))
+    return a

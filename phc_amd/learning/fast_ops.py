@@ -8,6 +8,8 @@
   With `+learning.params.config.wgrad=native` (`set_wgrad`) mask, weight gradient and bias gradient are ONE launch of the project's own MFMA kernel
   (`phc_wgrad_bf16`, csrc/phc_gemm.hip), fp32 up to the gradient bucket.
 * `FastLinearDD` -- the same, differentiable twice, for the discriminator MLP whose gradient penalty differentiates the backward pass.
+* `FusedSiLU`, `mse_loss` -- the student MLP of the distillation stage (phc_amd/distill.py): SiLU layers (`phc_silu_bf16`, `phc_colsum_silu_bf16`) and the
+  regression loss with its gradient (`phc_mse_loss`).
 * `ppo_loss`, `disc_bce`, `weighted_sumsq` -- the loss terms with their gradients as kernels (unit-weight convention, see `_PPOLossFn`).
 * `policy_sample` -- the rollout's sampling / neglogp / value un-normalisation in one kernel.
 * `adam_clip_step` -- clip_grad_norm_ + torch.optim.Adam.step on the flat parameter in two launches, also maintaining the bf16
@@ -167,6 +169,34 @@ def colsum_relu_bf16(gy, y, out=None):
     return gm, out
 
 
+def silu_bf16(z):
+    """z bf16 [rows, cols] (contiguous, device) -> silu(z) bf16 (`phc_silu_bf16`: fp32 arithmetic, one rounding)"""
+    rows, cols = z.shape
+    y = torch.empty_like(z)
+    L.check(L.load().phc_silu_bf16(z.data_ptr(), rows, cols, y.data_ptr(), _stream(z.device)), "phc_silu_bf16")
+    return y
+
+
+def colsum_silu_bf16(gy, z, out=None):
+    """(gy, z) bf16 [rows, cols] -> (gz = gy silu'(z), bf16 [rows, cols]; fp32 column sums of the unrounded products [cols], into `out` when given): the SiLU's
+    backward and the bias gradient of the layer in front in one pass, deferred like colsum_relu_bf16's."""
+    lib = L.load()
+    rows, cols = gy.shape
+    gz = torch.empty_like(gy)
+    if _defer(out):
+        assert out.numel() == cols and out.dtype == torch.float32 and out.is_contiguous()
+        ws = _workspace(("colsum", out.data_ptr()), lib.phc_colsum_workspace(rows, cols), gy.device, torch.float32)
+        L.check(lib.phc_colsum_silu_bf16(gy.data_ptr(), z.data_ptr(), rows, cols, gz.data_ptr(), None, ws.data_ptr(), _stream(gy.device)), "phc_colsum_silu_bf16")
+        _pend(ws, out, lib.phc_colsum_chunks(rows), cols)
+        return gz, out
+    if out is None:
+        out = torch.empty(cols, dtype=torch.float32, device=gy.device)
+    ws = _workspace("colsum", lib.phc_colsum_workspace(rows, cols), gy.device, torch.float32)
+    L.check(lib.phc_colsum_silu_bf16(gy.data_ptr(), z.data_ptr(), rows, cols, gz.data_ptr(), out.data_ptr(), ws.data_ptr(), _stream(gy.device)),
+            "phc_colsum_silu_bf16")
+    return gz, out
+
+
 SPLIT_K = 8
 
 
@@ -321,17 +351,24 @@ def _linear_grads_native(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype,
     return gz, gx, None, None if direct else gb
 
 
-def _linear_grads(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like=None, keep_gz=False):
+def _linear_grads(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like=None, keep_gz=False, silu=False):
     """First-order backward of a bf16 layer y = x W^T + b (and of the ReLU behind it when its output `y` is given) -> (gz, gx, gw, gb):
     gz = gy masked by y > 0, gx = gz W (brought to the width of `pad_like` when given, see _pad_like), gw = gz^T xb, gb = 1^T gz;
     gw / gb are None when they were stored or added in the parameter's bucket gradient (_wgrad_into, _first_write).
-    `keep_gz`: the caller reads gz (with `wgrad=native` it is only materialised for that or for gx)."""
+    `keep_gz`: the caller reads gz (with `wgrad=native` it is only materialised for that or for gx).
+    `silu`: `y` is the layer's PRE-activation z and the activation behind it a SiLU: gz = gy silu'(z) (phc_colsum_silu_bf16; the native kernel only knows the ReLU mask)."""
     gy = gy.contiguous()
-    dest = _native_dest(weight, gy, xb, y)
+    dest = None if silu else _native_dest(weight, gy, xb, y)
     if dest is not None:
         return _linear_grads_native(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_like, keep_gz, dest)
     gb = direct = None       # direct: the bias gradient goes straight into the bucket (None: not decided yet)
-    if y is not None:
+    if y is not None and silu:
+        # SiLU derivative and bias gradient in ONE pass over the output gradient (phc_colsum_silu_bf16)
+        direct = _first_write(bias) if need_gb else False
+        gy, gb = colsum_silu_bf16(gy.to(torch.bfloat16), y, out=bias.grad if direct else None)
+        if not need_gb:
+            gb, direct = None, None
+    elif y is not None:
         if need_gb and gy.dtype == torch.bfloat16:
             # ReLU mask and bias gradient in ONE pass over the output gradient (phc_colsum_relu_bf16)
             direct = _first_write(bias)
@@ -340,16 +377,21 @@ def _linear_grads(gy, xb, wb, weight, bias, y, need_gx, need_gb, x_dtype, pad_li
             gy = _relu_mask(gy, y)
     gx = _pad_like((gy @ wb).to(x_dtype), pad_like) if need_gx else None
     gw = _wgrad_into(weight, gy, xb)
-    if need_gb and direct is None:
+    if need_gb and direct is None and not silu:
         direct = _first_write(bias)
         gb = colsum_bf16(gy, out=bias.grad if direct else None)
     return gy, gx, gw, None if direct else gb
 
 
+ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2   # the activation a device layer carries (_LinearFn's `relu` argument; True == ACT_RELU)
+
+
 class _LinearFn(torch.autograd.Function):
     """`relu=True`: the layer AND the ReLU that follows it (round 2): hipBLASLt's epilogue applies it (`torch._addmm_activation`:
     bit-identical to addmm + relu, 36 -> 40 us instead of 52 for 16384 x 934 x 1024), the backward masks the incoming gradient with the
-    saved output before the weight / bias / input gradients are formed."""
+    saved output before the weight / bias / input gradients are formed.
+    `relu=2` (ACT_SILU): the layer and the SiLU behind it: the pre-activation z is kept, y = silu(z) is one pass (phc_silu_bf16), the backward forms
+    gy silu'(z) and the bias gradient in one pass (phc_colsum_silu_bf16)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
@@ -357,8 +399,11 @@ class _LinearFn(torch.autograd.Function):
             xb = x.to(torch.bfloat16)
             wb, bb = _bf16_params(weight, bias)
             wb, xb = _match_cols(wb, xb)
-            y = torch._addmm_activation(bb, xb, wb.t()) if relu else torch.addmm(bb, xb, wb.t())
-        if relu:
+            y = torch._addmm_activation(bb, xb, wb.t()) if relu == 1 else torch.addmm(bb, xb, wb.t())
+        if relu == ACT_SILU:
+            ctx.save_for_backward(xb, wb, y)
+            y = silu_bf16(y)
+        elif relu:
             ctx.save_for_backward(xb, wb, y)
         else:
             ctx.save_for_backward(xb, wb)
@@ -371,7 +416,7 @@ class _LinearFn(torch.autograd.Function):
         xb, wb = ctx.saved_tensors[:2]
         y = ctx.saved_tensors[2] if ctx.relu else None
         weight, bias = ctx.params
-        _, gx, gw, gb = _linear_grads(gy, xb, wb, weight, bias, y, ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.x_dtype)
+        _, gx, gw, gb = _linear_grads(gy, xb, wb, weight, bias, y, ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.x_dtype, silu=ctx.relu == ACT_SILU)
         return gx, gw, gb, None
 
 
@@ -770,7 +815,8 @@ class _SplitLinearFn(torch.autograd.Function):
 
 class FastLinear(_DeviceLinear):
     fuse_relu = False      # set by network.build_mlp when a ReLU follows: the device passes apply it in the GEMM epilogue
-    _fused_now = False     # did the last forward() apply it?  (read by the FusedReLU module that follows in the nn.Sequential)
+    fuse_silu = False      # set by network.build_mlp when a SiLU follows: the bf16 training pass applies it (phc_silu_bf16) and differentiates it with the bias sum
+    _fused_now = False     # did the last forward() apply it?  (read by the FusedReLU / FusedSiLU module that follows in the nn.Sequential)
     split_precision = False   # IMAmpAgent sets it on the actor's layers for `actor_precision=split_bf16`: fp32 activations in, fp32 out, three bf16 GEMMs per product
 
     def forward(self, x):
@@ -785,8 +831,8 @@ class FastLinear(_DeviceLinear):
         if self._device_pass(x):
             if self.out_features == 1 and x.dtype == torch.bfloat16:
                 return _Linear1Fn.apply(x, self.weight, self.bias)
-            self._fused_now = self.fuse_relu
-            return _LinearFn.apply(x, self.weight, self.bias, self.fuse_relu)
+            self._fused_now = self.fuse_relu or self.fuse_silu
+            return _LinearFn.apply(x, self.weight, self.bias, ACT_SILU if self.fuse_silu else int(self.fuse_relu))
         shadow = _bf16_params(self.weight, self.bias, cast=False) if self.bias is not None else None
         if shadow is not None and x.is_cuda and x.dtype == torch.bfloat16 and not torch.is_grad_enabled():
             # rollout inference inside FlatGradBucket.shadow_scope(): the bf16 parameter copies are current, no per-call casts
@@ -815,6 +861,60 @@ class FusedReLU(nn.ReLU):
             self._prev[0]._fused_now = False
             return x
         return super().forward(x)
+
+
+class FusedSiLU(nn.SiLU):
+    """The SiLU behind a FastLinear in an nn.Sequential (same position, no parameters: state-dict keys unchanged): a no-op when the layer in front of it has
+    already applied it in its training pass; on a bf16 device tensor outside autograd one `phc_silu_bf16` pass; nn.SiLU everywhere else."""
+
+    def __init__(self, prev):
+        super().__init__()
+        self._prev = [prev]     # (a list: not registered as a sub-module)
+
+    def forward(self, x):
+        if self._prev[0]._fused_now:
+            self._prev[0]._fused_now = False
+            return x
+        if x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous() and x.numel() > 0 and not (torch.is_grad_enabled() and x.requires_grad):
+            return silu_bf16(x)
+        return super().forward(x)
+
+
+class _MSELossFn(torch.autograd.Function):
+    """nn.MSELoss() of a network head against rows of a dataset (`phc_mse_loss`): forward computes the loss AND its gradient w.r.t. the head; backward hands
+    it out (as it is with `unit_grad`: the loss is then the root of the backward pass)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, row_index, unit_grad, out=None):
+        lib = L.load()
+        B, D = pred.shape
+        assert pred.is_contiguous() and pred.dtype in (torch.bfloat16, torch.float32)
+        assert target.dtype == torch.float32 and target.is_contiguous() and target.shape[1] == D and target.device == pred.device
+        assert row_index is None or (row_index.dtype == torch.int64 and row_index.is_contiguous() and row_index.numel() == B and row_index.device == pred.device)
+        assert row_index is not None or target.shape[0] == B
+        grad = torch.empty_like(pred)
+        buf = torch.empty(1, dtype=torch.float32, device=pred.device) if out is None else out
+        assert buf.numel() == 1 and buf.dtype == torch.float32
+        ws = _workspace("mse", lib.phc_mse_loss_workspace(), pred.device, torch.float64)
+        L.check(lib.phc_mse_loss(pred.data_ptr(), int(pred.dtype == torch.bfloat16), target.data_ptr(), None if row_index is None else row_index.data_ptr(), B, D,
+                                 grad.data_ptr(), buf.data_ptr(), ws.data_ptr(), _stream(pred.device)), "phc_mse_loss")
+        ctx.save_for_backward(grad)
+        ctx.unit_grad = unit_grad
+        return buf.view(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad if ctx.unit_grad else grad * g.to(grad.dtype)), None, None, None, None
+
+
+def mse_loss(pred, target, row_index=None, unit_grad=False, out=None):
+    """nn.MSELoss()(pred, target[row_index]) with its gradient in one pass on the device (pred bf16 or fp32 [B, D], target fp32 [R, D]); the torch expression
+    anywhere else."""
+    if pred.is_cuda and pred.dim() == 2 and pred.dtype in (torch.bfloat16, torch.float32) and pred.is_contiguous():
+        return _MSELossFn.apply(pred, target, row_index, unit_grad, out)
+    return nn.functional.mse_loss(pred.float(), target if row_index is None else target[row_index])
 
 
 class _PPOLossFn(torch.autograd.Function):

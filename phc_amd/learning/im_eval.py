@@ -67,7 +67,14 @@ def metrics_from_sums(sums, count, num_bodies):
     return m
 
 
-def _run_batch_host(agent, num_steps, own):
+def _begin_record(rec, lib, num_steps):
+    """`collect_dataset`: the batch's reset has run; the recorder seeds its previous-observation buffer and lays out the batch block."""
+    if rec is not None:
+        keys = getattr(lib, "curr_motion_keys", None)
+        rec.begin_batch(num_steps, lib._motion_data_keys[lib._curr_motion_ids.cpu().numpy()] if keys is None else keys)
+
+
+def _run_batch_host(agent, num_steps, own, rec=None):
     """One batch of the sweep with the metrics formed on the host: every step's body positions are copied back and kept until the batch ends.
     -> (failed flags of the batch's `own` clips, {metric: per-clip values, NaN where a clip is too short})."""
     task, env = agent.task, agent.vec_env
@@ -76,10 +83,13 @@ def _run_batch_host(agent, num_steps, own):
     terminate_state = torch.zeros(N, device=task.device, dtype=torch.bool)
     preds, gts = [], []
     obs = env.reset()
+    _begin_record(rec, lib, num_steps)
     curr = 0
     while True:
         res = agent.get_action_values(obs)
         obs, r, done, info = env.step(agent.preprocess_actions(res["mus"]))  # deterministic policy (is_determenistic=True)
+        if rec is not None:
+            rec.record()
         # a termination after the clip's last frame is not a failure (im_amp.py:248)
         term = torch.logical_and(torch.as_tensor(curr <= num_steps - 1, device=task.device), info["terminate"].bool())
         terminate_state |= term
@@ -102,13 +112,15 @@ def _run_batch_host(agent, num_steps, own):
         curr += 1
         if curr >= curr_max or not alive.any():
             break
+    if rec is not None:
+        rec.end_batch()
     P, G = np.stack(preds), np.stack(gts)
     frames = [max(min(int(num_steps[i]) - 1, P.shape[0]), 0) for i in range(own)]
     m = compute_metrics_per_clip([P[:n, i] for i, n in enumerate(frames)], [G[:n, i] for i, n in enumerate(frames)])
     return terminate_state.cpu().numpy()[:own], m
 
 
-def _run_batch_device(agent, num_steps_dev, num_steps, own):
+def _run_batch_device(agent, num_steps_dev, num_steps, own, rec=None):
     """The same batch with `eval_metrics=device`: `HumanoidIm.post_physics_step` adds every step's error sums to per-env device totals
     (phc_eval_accumulate) and the loop reads back two integers per step -- how many envs are alive and the longest clip among them -- from which
     `curr_max` follows by the host loop's rules, so the batch runs exactly as many env steps.  One copy of the totals ends the batch."""
@@ -118,10 +130,13 @@ def _run_batch_device(agent, num_steps_dev, num_steps, own):
     last = np.flatnonzero(lib._curr_motion_ids.cpu().numpy() == U - 1)   # (the clips of a batch are fixed: once, not per step)
     task.begin_eval_accumulation(num_steps_dev, int(last[0]) + 1 if len(last) else N)
     obs = env.reset()
+    _begin_record(rec, lib, num_steps)
     curr = 0
     while True:
         res = agent.get_action_values(obs)
         obs, r, done, info = env.step(agent.preprocess_actions(res["mus"]))
+        if rec is not None:   # (one launch behind the post-physics launch; nothing is copied back)
+            rec.record()
         n_alive, curr_max = task.eval_status()
         if n_alive:
             if curr >= curr_max:   # (also "nobody below the bound is alive": status gives 0 there, the host loop curr - 1)
@@ -131,6 +146,8 @@ def _run_batch_device(agent, num_steps_dev, num_steps, own):
         curr += 1
         if curr >= curr_max or not n_alive:
             break
+    if rec is not None:
+        rec.end_batch()
     fail, sums, count = (t.cpu().numpy()[:own] for t in task.end_eval_accumulation())
     return fail != 0, metrics_from_sums(sums, count, task.num_bodies)
 
@@ -148,6 +165,9 @@ def evaluate(agent, output_dir=None, log=print):
     if mode not in ("host", "device"):
         raise ValueError(f"learning.params.config.eval_metrics must be host or device, not {mode!r}")
     device_metrics = mode == "device"
+    dist0 = getattr(agent, "dist", None)
+    if getattr(task, "collect_dataset", False) and dist0 is not None and dist0.is_initialized() and dist0.get_world_size() > 1:
+        raise ValueError(f"collect_dataset=True records in one process, not on {dist0.get_world_size()} ranks")
     agent.set_eval()
     lib_train = task._motion_lib
     saved = dict(td=task._termination_distances.clone(), test=flags.test, im_eval=flags.im_eval, start_idx=task.start_idx)
@@ -160,6 +180,13 @@ def evaluate(agent, output_dir=None, log=print):
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     num_batches = (U + N - 1) // N
+    # `collect_dataset=True`: record (observation, clean action, noisy action, reset) rows of every clip, wrapped-around duplicates of the last batch included
+    # (learning/dataset_record.py); the reference records in one process
+    rec = None
+    if getattr(task, "collect_dataset", False):
+        from .dataset_record import DatasetRecorder
+        rec = DatasetRecorder(task)
+    agent.last_dataset = None
     push = getattr(task, "_push", None)                         # `+perturb.*` (phc_amd/perturb.py): the sweep then runs under scheduled pushes
     pushes0 = int(push.pushes) if push is not None else 0
     failed = np.zeros(U, dtype=np.float64)                      # 1 where the clip terminated before its last frame
@@ -178,9 +205,9 @@ def evaluate(agent, output_dir=None, log=print):
                 own = min(N, U - bi * N)                          # the envs past the library's end hold duplicates of its first clips
                 clips = slice(bi * N, bi * N + own)
                 if device_metrics:
-                    failed[clips], m = _run_batch_device(agent, num_steps_dev, num_steps, own)
+                    failed[clips], m = _run_batch_device(agent, num_steps_dev, num_steps, own, rec)
                 else:
-                    failed[clips], m = _run_batch_host(agent, num_steps, own)
+                    failed[clips], m = _run_batch_host(agent, num_steps, own, rec)
                 for k in METRICS:
                     per_clip[k][clips] = np.nan_to_num(m[k])
                     have[k][clips] = ~np.isnan(m[k])
@@ -220,6 +247,11 @@ def evaluate(agent, output_dir=None, log=print):
         lib_train.update_hard_sampling_weight(list(failed_keys))
     elif task.auto_pmcp_soft:
         lib_train.update_soft_sampling_weight(list(failed_keys))
+    if rec is not None:   # the player's dump (im_amp_players.py:200-214), after the last batch
+        rms = getattr(agent, "running_mean_std", None)
+        agent.last_dataset = rec
+        if output_dir is not None:
+            rec.dump(output_dir, None if rms is None else {k: v.detach().cpu() for k, v in rms.state_dict().items()}, log=log)
     # rank 0 alone writes -- atomically, so that `restore()` can never pick up a torn file
     if output_dir is not None and getattr(agent, "rank", 0) == 0:
         os.makedirs(output_dir, exist_ok=True)

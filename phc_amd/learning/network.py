@@ -15,7 +15,7 @@ import os
 import torch
 from torch import nn
 
-from .fast_ops import FastLinear, FastLinear1DD, FastLinearDD, FusedReLU
+from .fast_ops import FastLinear, FastLinear1DD, FastLinearDD, FusedReLU, FusedSiLU
 
 DISC_LOGIT_INIT_SCALE = 1.0  # amp_network_builder.py:12
 
@@ -40,6 +40,9 @@ def build_mlp(input_size, units, activation, linear=nn.Linear):
         if activation == "relu" and isinstance(lin, (FastLinear, FastLinearDD)):   # the ReLU rides in the GEMM epilogue of the device passes
             lin.fuse_relu = True
             layers += [lin, FusedReLU(lin)]
+        elif activation == "silu" and type(lin) is FastLinear:   # SiLU and its derivative are passes of their own next to the GEMM (phc_silu_bf16, phc_colsum_silu_bf16)
+            lin.fuse_silu = True
+            layers += [lin, FusedSiLU(lin)]
         else:
             layers += [lin, _ACT[activation]()]
         n = u

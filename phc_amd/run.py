@@ -46,6 +46,13 @@ def main(argv=None):
         ckpt = cand if os.path.exists(cand) else None
     if ckpt:
         agent.restore(ckpt, load_optimizer=not cfg.test)
+    student = (cfg.get("student", None) or {}).get("checkpoint", None)
+    if student:
+        # `+student.checkpoint=<NNNNN.pth>` (phc_amd/distill.py): a distilled MLP acts in place of the policy, in `play` and in the sweep alike
+        if not cfg.test:
+            raise ValueError("+student.checkpoint plays a distilled student: it needs test=True")
+        from .distill import StudentPolicy
+        agent = StudentPolicy(agent, str(student))
     if cfg.test:
         # player mode (phc/learning/im_amp_players.py:25-384): no learning; im_eval=True sweeps the whole motion set and reports the
         # success rate / MPJPE table, otherwise a deterministic-policy rollout of `games` env steps reports episode statistics
