@@ -123,7 +123,9 @@ DEFAULT_PARAMS = dict(gravity_z=-9.81, contact_stiffness=1.0e5, contact_damping=
                       self_collision=0, self_stiffness_scale=0.25, self_damping_ratio=0.5,
                       # ground-contact model (include/phc_amd.h, ABI 34): 0 penalty, 1 rigid ("tgs")
                       contact_model=0, contact_iterations=4, contact_impedance=1.0e5, max_depenetration_velocity=10.0,
-                      bounce_threshold_velocity=0.2, restitution=0.0, contact_offset=0.02)
+                      bounce_threshold_velocity=0.2, restitution=0.0, contact_offset=0.02,
+                      # body-body forces in fixed point like the stepper: (force steps per N, moment steps per N m), e.g. (1024, 4096); None: floating point
+                      self_force_fixed_point=None)
 
 
 def kinematics(model, st):
@@ -158,8 +160,10 @@ def body_velocities(model, st, R, p):
     return w, v
 
 
-def seg_seg_closest(p1, q1, p2, q2):
-    """Closest points of two segments (Ericson, Real-Time Collision Detection 5.1.9); degenerate segments are points."""
+def seg_seg_closest(p1, q1, p2, q2, info=None):
+    """Closest points of two segments (Ericson, Real-Time Collision Detection 5.1.9); degenerate segments are points.
+    `info` (a dict, branch witness): which branch the general case took -- `kind` interior | end_s | end_t | end_end -- and the unclamped parameters that decided it
+    (`s_raw`, `t_raw`, `s2_raw` of the re-solve, `par` = denom / (a e) of the parallel test)."""
     d1, d2, r = q1 - p1, q2 - p2, p1 - p2
     a, e, f = d1 @ d1, d2 @ d2, d2 @ r
     EPS = 1e-10
@@ -177,6 +181,12 @@ def seg_seg_closest(p1, q1, p2, q2):
             denom = a * e - b * b
             s = min(max((b * f - c * e) / denom, 0.0), 1.0) if denom > 1e-7 * a * e else 0.0
             t = (b * s + f) / e
+            if info is not None:
+                s_raw = (b * f - c * e) / denom if denom > 1e-7 * a * e else None
+                s2_raw = None if 0 <= t <= 1 else ((-c / a) if t < 0 else ((b - c) / a))
+                s_end = (s_raw is None or not 0.0 < s_raw < 1.0) if s2_raw is None else (not 0.0 < s2_raw < 1.0)
+                info.update(s_raw=s_raw, t_raw=t, s2_raw=s2_raw, par=denom / (a * e),
+                            kind=(("end_s" if s_end else "interior") if s2_raw is None else ("end_end" if s_end else "end_t")))
             if t < 0:
                 t, s = 0.0, min(max(-c / a, 0.0), 1.0)
             elif t > 1:
@@ -184,7 +194,7 @@ def seg_seg_closest(p1, q1, p2, q2):
     return p1 + d1 * s, p2 + d2 * t
 
 
-def self_collision_wrenches(model, R, p, w, v, prm, dt):
+def self_collision_wrenches(model, R, p, w, v, prm, dt, trace=None):
     """Explicit capsule-capsule penalty forces between the collision SHAPES that may collide (model.collision_pairs(): a body may carry more
     than one capsule since round 4): (F[NB,3], N[NB,3] about each body origin)."""
     nb = model.num_bodies
@@ -195,10 +205,13 @@ def self_collision_wrenches(model, R, p, w, v, prm, dt):
     for s1, s2 in model.collision_pairs():
         for a, b in ((s1, s2), (s2, s1)):      # both directions: each owner receives its own force
             i, k = int(own[a]), int(own[b])
-            c1, c2 = seg_seg_closest(A[a], B[a], A[b], B[b])
+            info = {} if trace is not None and a == s1 else None   # (the witness records the direction the stepper evaluates: first shape -> second shape)
+            c1, c2 = seg_seg_closest(A[a], B[a], A[b], B[b], info)
             n = c1 - c2
             dist = np.linalg.norm(n)
             pen = cap[a, 6] + cap[b, 6] - dist
+            if info:
+                trace.append(dict(info, shapes=(int(s1), int(s2)), pen=float(pen)))
             if pen <= 0:
                 continue
             n = n / dist if dist > 1e-6 else np.array([0.0, 0.0, 1.0])
@@ -209,6 +222,14 @@ def self_collision_wrenches(model, R, p, w, v, prm, dt):
             cc = 2.0 * prm["self_damping_ratio"] * np.sqrt(kk * mu)
             fn = kk * pen - cc * (vrel @ n)
             if fn <= 0:
+                continue
+            if prm.get("self_force_fixed_point"):
+                # the stepper adds body-body forces and moments in fixed point (integer atomics, so that the sums do not depend on the order the lanes arrive in:
+                # csrc/phc_aba.h aba_pair_narrow): force rounded to 1 / fs N, then its moment about each body's origin to 1 / ns N m
+                fs, ns = prm["self_force_fixed_point"]
+                Fq = np.rint(n * fn * fs) / fs
+                F[i] += Fq
+                N[i] += np.rint(cross3(cp - p[i], Fq) * ns) / ns
                 continue
             F[i] += n * fn
             N[i] += cross3(cp - p[i], n * fn)
@@ -224,12 +245,16 @@ def explicit_torque(model, st, target, kp_scale=1.0, kd_scale=1.0):
     tau = sp - model.dof_kd * kd_scale * qd
     sat = np.abs(tau) >= model.dof_effort
     # (held torque of mode 1, [spring-or-limit, saturated flag] of mode 2)
-    return np.clip(tau, -model.dof_effort, model.dof_effort), np.where(sat, np.sign(tau) * model.dof_effort, sp), sat
+    # (and, for the branch witness, the torque before the clamp)
+    return np.clip(tau, -model.dof_effort, model.dof_effort), np.where(sat, np.sign(tau) * model.dof_effort, sp), sat, tau
 
 
-def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, return_parts=False, tau_hold=None, nud_prev=None, cstate=None):
+def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, return_parts=False, tau_hold=None, nud_prev=None, cstate=None, trace=None):
     """Generalized accelerations nu_dot = [alpha0, a0, qdd_1..] of one implicit sub-step.  `nud_prev` (rigid contact model): the solution of
-    the previous pass of this sub-step -- active set and friction cone are evaluated on the end-of-step velocities it predicts."""
+    the previous pass of this sub-step -- active set and friction cone are evaluated on the end-of-step velocities it predicts.
+    `trace` (a dict, branch witness; see sim_step): filled with this evaluation's `contacts`, `pairs` and `effort_ratio`.  Recording changes no number."""
+    if trace is not None:
+        trace.update(contacts=[], pairs=[], effort_ratio=np.zeros(model.num_dof))
     prm = dict(DEFAULT_PARAMS, **(params or {}))
     nb = model.num_bodies
     offs = np.concatenate([[6], 6 + np.cumsum(st.nd)]).astype(int)
@@ -286,6 +311,11 @@ def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, ret
             depth = rad - (p[i][2] + arm[2])
             if prm["contact_model"] == 1:
                 # rigid: unilateral velocity constraint u_n(t + dt) >= v_target through the impedance c; active set and cone from the previous pass
+                rec = None
+                if trace is not None:
+                    rec = dict(point=int(k), body=int(i), depth=float(depth), kind="outside" if depth <= -prm["contact_offset"] else ("penetrating" if depth > 0 else "speculative"),
+                               active=False)
+                    trace["contacts"].append(rec)
                 if depth <= -prm["contact_offset"]:
                     continue
                 c = prm["contact_impedance"]
@@ -295,9 +325,17 @@ def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, ret
                 Jpt = Jv[i] - skew(arm) @ Jw[i]
                 un = uc if nud_prev is None else uc + dt * (Jpt @ nud_prev + apb)
                 vt = min(depth / dt, prm["max_depenetration_velocity"]) if depth > 0 else depth / dt
+                if rec is not None:
+                    rec.update(approach=float(-uc[2]), depen_ratio=float(depth / dt / prm["max_depenetration_velocity"]) if depth > 0 else None,
+                               depen_capped=bool(depth > 0 and depth / dt > prm["max_depenetration_velocity"]),
+                               bounce_ratio=float(-uc[2] / prm["bounce_threshold_velocity"]) if prm["restitution"] > 0 else None,
+                               bounced=bool(prm["restitution"] > 0 and -uc[2] > prm["bounce_threshold_velocity"]),
+                               bounce_over_depen=float(-prm["restitution"] * uc[2] / vt) if vt > 0 else float("inf"))
                 if prm["restitution"] > 0 and -uc[2] > prm["bounce_threshold_velocity"]:
                     vt = max(vt, -prm["restitution"] * uc[2])
                 lam = c * (vt - un[2])
+                if rec is not None:
+                    rec.update(lam=float(lam))
                 if lam <= 0:   # idle -- or released: it pushed in the last pass and would have to pull (phc_aba.h aba_ground_contact_rigid)
                     if k in cstate["active"]:
                         cstate["removed"].add(k)
@@ -306,20 +344,32 @@ def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, ret
                     continue
                 act_now.add(k)
                 ct = rigid_ct(prm, lam, uc, un)
+                if rec is not None:
+                    cone = prm["friction"] * lam / (max(np.hypot(uc[0], uc[1]), np.hypot(un[0], un[1])) + 1e-9) / prm["contact_impedance"]
+                    rec.update(active=True, cone_ratio=float(cone), friction="stick" if cone >= 1.0 else "slip")
                 Cm = np.diag([ct, ct, c])
                 F0 = np.array([-ct * uc[0], -ct * uc[1], c * (vt - uc[2])])
                 M += dt * Jpt.T @ Cm @ Jpt
                 rhs += Jpt.T @ (F0 - dt * Cm @ apb)
                 continue
+            rec = None
+            if trace is not None:
+                rec = dict(point=int(k), body=int(i), depth=float(depth), kind="penetrating" if depth > 0 else "outside", active=False)
+                trace["contacts"].append(rec)
             if depth <= 0:
                 continue
             arm = arm - np.array([0, 0, rad])
             uc = v[i] + cross3(w[i], arm)
             fn0 = prm["contact_stiffness"] * depth - cn * uc[2]
+            if rec is not None:
+                rec.update(fn0=float(fn0))
             if fn0 <= 0:
                 continue
             ut = np.hypot(uc[0], uc[1])
             ct = min(prm["friction_viscous"], prm["friction"] * fn0 / (ut + 1e-6))
+            if rec is not None:
+                cone = prm["friction"] * fn0 / (ut + 1e-6) / prm["friction_viscous"]
+                rec.update(active=True, slip_speed=float(ut), cone_ratio=float(cone), friction="stick" if cone >= 1.0 else "slip")
             Cm = np.diag([ct, ct, cn])
             F0 = np.array([-ct * uc[0], -ct * uc[1], fn0])
             fcontact[i] += F0 - dt * Cm @ cross3(w[i], cross3(w[i], arm))
@@ -328,7 +378,7 @@ def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, ret
             M += dt * Jpt.T @ Cm @ Jpt
             rhs += Jpt.T @ (F0 - dt * Cm @ apb)
     if prm["self_collision"]:
-        Fs, Ns = self_collision_wrenches(model, R, p, w, v, prm, dt)
+        Fs, Ns = self_collision_wrenches(model, R, p, w, v, prm, dt, None if trace is None else trace["pairs"])
         for i in range(nb):
             rhs += Jw[i].T @ Ns[i] + Jv[i].T @ Fs[i]
             fcontact[i] += Fs[i]
@@ -346,6 +396,8 @@ def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, ret
             err = quat_to_rotvec(quat_mul(quat_conj(st.q[i - 1]), qt))
         else:
             err = np.asarray(target[s:s + 1], dtype=np.float64) - st.theta[i - 1]
+        if trace is not None:   # what the effort clamp decides on: the spring term (implicit drive) or the whole explicit torque as it was held
+            trace["effort_ratio"][s:s + n] = kp * err / eff if prm["control_mode"] == 0 else tau_hold[3][s:s + n] / eff
         if prm["control_mode"] == 1:   # explicit torque held over the simulate call
             tau = np.array(tau_hold[0][s:s + n], dtype=np.float64)
             d = arm_.copy()
@@ -410,15 +462,17 @@ def rigid_contact_forces(model, parts, prm, dt, nud, active):
     return F
 
 
-def substep(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, tau_hold=None):
-    """One linearly-implicit sub-step; returns the applied joint torques (S5)."""
+def substep(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, tau_hold=None, trace=None):
+    """One linearly-implicit sub-step; returns the applied joint torques (S5).  `trace`: this sub-step's record of the branch witness (sim_step)."""
     prm = dict(DEFAULT_PARAMS, **(params or {}))
-    nud, parts = accelerations(model, st, target, prm, dt, kp_scale, kd_scale, return_parts=True, tau_hold=tau_hold)
+    nud, parts = accelerations(model, st, target, prm, dt, kp_scale, kd_scale, return_parts=True, tau_hold=tau_hold, trace=trace)
     if prm["contact_model"] == 1:
         cstate = {"active": set(), "removed": set()}
-        nud, parts = accelerations(model, st, target, prm, dt, kp_scale, kd_scale, return_parts=True, tau_hold=tau_hold, cstate=cstate)
+        nud, parts = accelerations(model, st, target, prm, dt, kp_scale, kd_scale, return_parts=True, tau_hold=tau_hold, cstate=cstate, trace=trace)
+        if trace is not None:
+            trace["contacts_first_pass"] = trace["contacts"]
         for _ in range(1, max(1, int(prm["contact_iterations"]))):   # passes on active set and friction cone
-            nud, parts = accelerations(model, st, target, prm, dt, kp_scale, kd_scale, return_parts=True, tau_hold=tau_hold, nud_prev=nud, cstate=cstate)
+            nud, parts = accelerations(model, st, target, prm, dt, kp_scale, kd_scale, return_parts=True, tau_hold=tau_hold, nud_prev=nud, cstate=cstate, trace=trace)
         parts["fcontact"] = rigid_contact_forces(model, parts, prm, dt, nud, cstate["active"]) + parts["fcontact"]
     damp = 1.0 / (1.0 + dt * prm["angular_damping"])
     st.w0 = (st.w0 + dt * nud[0:3]) * damp
@@ -435,6 +489,8 @@ def substep(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, tau_hold=
         tau_applied.append(parts["tau"][i] - (parts["dimp"][i] - model.dof_armature[s:s + n]) * qdd)
         wj = (st.qd[i - 1] + dt * qdd) * damp
         nrm = np.linalg.norm(wj)
+        if trace is not None:
+            trace.setdefault("rate_ratio", np.zeros(nb - 1))[i - 1] = nrm / prm["max_angular_velocity"]
         if nrm > prm["max_angular_velocity"]:
             wj = wj * (prm["max_angular_velocity"] / nrm)
         st.qd[i - 1] = wj
@@ -448,9 +504,21 @@ def substep(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, tau_hold=
 
 
 def sim_step(model, root_states, dof_state, pd_target, params=None, sim_dt=1 / 60, substeps=2, num_sim_calls=2,
-             kp_scale=1.0, kd_scale=1.0):
+             kp_scale=1.0, kd_scale=1.0, trace=None):
     """num_sim_calls x gym.simulate, each `substeps` sub-steps of sim_dt/substeps.  Returns new
-    (root_states[13], dof_state[D,2], rigid_body_state[NB,13], dof_force[D], contact_force[NB,3])."""
+    (root_states[13], dof_state[D,2], rigid_body_state[NB,13], dof_force[D], contact_force[NB,3]).
+
+    `trace` (a dict; None: nothing is recorded): the BRANCH WITNESS.  trace["substeps"] gets one record per sub-step saying which side of every data-dependent branch
+    of the scheme this fp64 evaluation took, with the quantity that decided it as a ratio to its branch point (tests/stepper_regimes.py asserts regimes and margins on
+    it; the fp32 stepper is not asked):
+      rate_ratio[joint]      |joint rate| / max_angular_velocity before the cap (> 1: capped)
+      effort_ratio[dof]      spring torque kp err / effort limit (implicit drive), or the whole explicit torque / limit as held (`pd` modes); |.| >= 1: saturated
+      contacts               per ground-contact point looked at: kind outside | penetrating | speculative, depth, active (it pushes), and where they apply
+                             depen_ratio / depen_capped, bounce_ratio / bounced / bounce_over_depen, cone_ratio and friction stick | slip
+                             (rigid model: of the LAST active-set pass; `contacts_first_pass` keeps pass 0's)
+      pairs                  per candidate capsule pair that reached the general closest-point case: kind interior | end_s | end_t | end_end, s_raw, t_raw, s2_raw,
+                             par = denom / (a e), pen
+    Recording changes no number: with and without it the results are equal bit for bit."""
     st = State(root_states, dof_state, model)
     dt = sim_dt / substeps
     tau = np.zeros(model.num_dof)
@@ -460,7 +528,10 @@ def sim_step(model, root_states, dof_state, pd_target, params=None, sim_dt=1 / 6
     for k in range(num_sim_calls * substeps):
         if explicit and k % substeps == 0:
             hold = explicit_torque(model, st, pd_target, kp_scale, kd_scale)
-        tau, fc = substep(model, st, pd_target, params, dt, kp_scale, kd_scale, tau_hold=hold)
+        rec = None if trace is None else {}
+        tau, fc = substep(model, st, pd_target, params, dt, kp_scale, kd_scale, tau_hold=hold, trace=rec)
+        if trace is not None:
+            trace.setdefault("substeps", []).append(rec)
     Q, R, p = kinematics(model, st)
     w, v = body_velocities(model, st, R, p)
     rbs = np.concatenate([p, np.array(Q), v, w], axis=-1)

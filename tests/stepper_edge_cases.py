@@ -99,9 +99,15 @@ def _shape_models():
     return models
 
 
+MODEL_MAKERS = {}   # {model name: be -> (ArticulationModel, model struct, keep)} for models a case table adds on top of the shipped ones (tests/stepper_regimes.py)
+
+
 def models_on(be, case):
     """-> ([ArticulationModel per shape block], model struct, what the struct points to), once per backend and model."""
     def make():
+        if case.model in MODEL_MAKERS:
+            m, ms, keep = MODEL_MAKERS[case.model](be)
+            return [m], ms, keep
         if case.model != "smpl_shapes":
             m, ms, keep = model_on(be, name=case.model)
             return [m], ms, keep
