@@ -28,9 +28,10 @@ MI355X-first differences (results-preserving):
     this file (`_ppo_loss_torch`, `_disc_loss`, RunningMeanStd's CPU branch) remain the CPU path and the definition those kernels
     are tested against.
 
-`IMAmpAgent` owns the reference's agent surface, the rollout (`play_steps`: eager, segment graphs, whole-step graphs), the dataset and its
-minibatch draw, checkpoints, and ONE definition of the optimizer step: `_fwd_bwd` dispatches to `_device_step` (`_policy_pass` + `_disc_pass`, on
-two streams or one) or to the torch path; `update_graph.CapturedUpdate` captures those same methods.  `__init__` assigns every attribute.
+`IMAmpAgent` owns the reference's agent surface, the dataset and its minibatch draw, checkpoints, ONE definition of the rollout step -- `_rollout_step` on the device
+(reset rule, `_rollout_policy`, env step, AMP row, `_rollout_after`), `_rollout_step_torch` on CPU tensors; `rollout_graph.CapturedRollout` captures those same methods,
+per segment or as whole steps, and owns the graphs, their pool and the rule that drops them -- and ONE definition of the optimizer step: `_fwd_bwd` dispatches to
+`_device_step` (`_policy_pass` + `_disc_pass`, on two streams or one) or to the torch path; `update_graph.CapturedUpdate` captures those same methods.  `__init__` assigns every attribute.
 """
 import copy
 import os
@@ -48,6 +49,7 @@ from .replay_buffer import ReplayBuffer
 from .fast_ops import (FastLinear, adam_clip_step, deferred_colsums, disc_bce, input_grad_only, param_grad_only, policy_sample, ppo_loss, register_lane, rows_with_grad,
                        set_wgrad, weighted_sumsq)
 from .running_mean_std import RunningMeanStd
+from .rollout_graph import CapturedRollout, call_segment
 from .update_graph import CapturedUpdate
 
 
@@ -393,7 +395,7 @@ class IMAmpAgent:
         self._ones_key = self._ones = None           # cotangent that selects the demo rows (_demo_row_mask)
         self._terminated_flags = self._terminated_mask = self._env_actions = None   # rollout scratch (play_steps)
         self._reward_raw_acc = None        # sum of the rollout's raw reward terms: made by the FIRST rollout, eagerly (whole-step graphs need it to exist)
-        self._roll_graphs, self._roll_pool, self._roll_generation = {}, None, None   # rollout hipGraphs by key, their memory pool, the task's launch generation they hold
+        self._rollout = CapturedRollout(self)              # the rollout steps as replayed hipGraphs (rollout_graph.py)
         self._summary_file = self._summary_writer = None      # _log_train_info
 
     # ------------------------------------------------------------------ modes (rl_games set_eval / set_train + amp_agent.py:63-82)
@@ -481,198 +483,136 @@ class IMAmpAgent:
     def env_reset(self, env_ids=None):
         return self.vec_env.reset(env_ids)
 
-    # ---- rollout segments as hipGraphs ----------------------------------------------------------------------------------------------
-    # scripts/profile_rollout.py: the rollout is HOST-bound (32 steps: 16.0 ms of launch / Python time for ~9.6 ms of device work).  With
-    # `hip_graph` the two policy segments of every rollout step -- (A) normalise + actor + critic + sampling into row n of the experience
-    # buffer, (B) the copies of the step's outputs, the next-value critic and the episode bookkeeping -- are captured once per row n (their
-    # inputs are the task's static buffers, their outputs rows of the persistent experience buffer) and replayed; the env itself (reset of
-    # finished envs, stepper, post-physics) keeps its three eager launches, since its host side carries state (RNG counter, reset lists).
-    def _rollout_graphs_enabled(self):
-        return (self.exp["obses"].is_cuda and self._use_graph and not self._graph_failed and self.epoch_num >= 2 and not self.faithful_reset
-                and hasattr(self.task, "reset_done") and not np.isfinite(self.vec_env.clip_obs) and not os.environ.get("PHC_NO_GRAPH")
-                and not os.environ.get("PHC_NO_ROLLOUT_GRAPH"))
+    # ---- one rollout step: the reset rule, the two policy segments, the bookkeeping, and one body per family of regimes ------------------------------
+    # (device: eager launches, segment graphs or whole-step graphs -- rollout_graph.py says which and owns the graphs; torch: CPU tensors)
+    _roll_graphs = property(lambda self: self._rollout.graphs)            # read by tests and probes
+    _roll_pool = property(lambda self: self._rollout.pool)
+    _roll_generation = property(lambda self: self._rollout.generation)
 
-    def _replay(self, key, fn):
-        g = self._roll_graphs.get(key)
-        if g is None:
-            in_group = self.dist is not None and self.dist.is_initialized()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            if self._roll_pool is None:   # the rollout graphs replay one after the other and leave their results in the
-                self._roll_pool = torch.cuda.graph_pool_handle()   # persistent experience buffers: their temporaries can share one pool
-            with torch.cuda.graph(g, pool=self._roll_pool, capture_error_mode="thread_local" if in_group else "global"):
-                fn()
-            self._roll_graphs[key] = g
-        g.replay()
+    def _rollout_reset(self, n):
+        """The reset in front of step n and the step's observation -> self.obs."""
+        task = self.task
+        # The reference starts every rollout with `done_indices = []` (amp_agent.py:313): the envs that finished on the LAST step of the previous
+        # rollout are not reset at step 0 -- they run one more step, are flagged again by that step's `_compute_reset` (their clip is still over /
+        # they are still down) and are reset at step 1.  Kept: one in `horizon_length` episode ends carries that extra transition in the reference's
+        # data too (tests/test_learner_epoch.py pins it).
+        if self.faithful_reset or not hasattr(task, "reset_done"):   # (a task without the device-side reset gets the reference's index list)
+            self.obs = self.env_reset(self.dones.nonzero(as_tuple=False)[:, 0] if n > 0 else [])
+            return
+        if n > 0:
+            task.reset_done()
+        clip = self.vec_env.clip_obs   # finite: clamp straight into the experience buffer row
+        self.obs = torch.clamp(task.obs_buf, -clip, clip, out=self.exp["obses"][n]) if np.isfinite(clip) else task.obs_buf
+
+    def _rollout_policy(self, n):
+        """(A) observation row, policy + value heads, sampling -> row n of the experience buffer."""
+        e, net = self.exp, self.model.a2c_network
+        if self.obs.data_ptr() != e["obses"][n].data_ptr():
+            e["obses"][n].copy_(self.obs)
+        processed = self._preproc_obs(self.obs)
+        with self._autocast():
+            mu, logstd = net.eval_actor(self._actor_obs(self.obs) if self._actor_split else processed)
+            value = net.eval_critic(processed)
+        if self._actor_split:
+            value = value.float()       # (one dtype flag for both heads in phc_policy_sample)
+        policy_sample(mu.contiguous(), value.contiguous(), (logstd[0] if logstd.dim() == 2 else logstd).float().contiguous(), self.value_mean_std,
+                      e["actions"][n], e["mus"][n], e["sigmas"][n], e["neglogpacs"][n], e["values"][n])
+        if self.clip_actions:
+            self.preprocess_actions(e["actions"][n], out=self._env_actions)
+
+    def _rollout_bookkeeping(self, n, rewards, terminate, reward_raw):
+        """The step's outputs into row n of the experience buffer and the episode bookkeeping (amp_agent.py:321-341): rewards / dones rows, terminated flags,
+        reward-term sums, episode statistics.  -> the step's `terminate` mask as floats."""
+        e = self.exp
+        e["next_obses"][n].copy_(self.obs)
+        if self._reward_raw_acc is None:
+            self._reward_raw_acc = torch.zeros(reward_raw.shape[1], dtype=reward_raw.dtype, device=self.device)
+        if (rewards.is_cuda and rewards.dtype == torch.float32 and rewards.is_contiguous() and self.dones.dtype == torch.int64 and terminate.dtype == torch.int64
+                and reward_raw.dtype == torch.float32 and reward_raw.is_contiguous() and reward_raw.shape[1] <= 8):   # on the device: one launch
+            L.check(L.load().phc_rollout_bookkeeping(
+                rewards.data_ptr(), float(self.reward_scale), self.dones.data_ptr(), terminate.data_ptr(), reward_raw.data_ptr(), reward_raw.shape[1],
+                self.num_actors, e["rewards"][n].data_ptr(), e["dones"][n].data_ptr(), self._terminated_flags.data_ptr(), self._terminated_mask.data_ptr(),
+                self._reward_raw_acc.data_ptr(), self.current_rewards.data_ptr(), self.current_lengths.data_ptr(),
+                torch.cuda.current_stream().cuda_stream), "phc_rollout_bookkeeping")
+            return self._terminated_mask
+        # the torch statement: the CPU path, the device's fallback for other dtypes / layouts, and what the launch is tested against
+        e["rewards"][n].copy_(rewards if self.reward_scale == 1 else rewards * self.reward_scale)
+        e["dones"][n].copy_(self.dones)
+        terminated = terminate.float()
+        self._terminated_flags.add_(terminated)
+        self._reward_raw_acc.add_(reward_raw.mean(dim=0))
+        not_dones = 1.0 - self.dones.float()
+        self.current_rewards.add_(rewards).mul_(not_dones.unsqueeze(1))
+        self.current_lengths.add_(1).mul_(not_dones)
+        return terminated
+
+    def _rollout_after(self, n, rewards, terminate, reward_raw):
+        """(B) the step's outputs into row n and the bookkeeping, next-value critic (zeroed where the episode terminated)."""
+        terminated = self._rollout_bookkeeping(n, rewards, terminate, reward_raw)
+        with self._autocast():
+            value = self.model.a2c_network.eval_critic(self._preproc_obs(self.obs))
+        policy_sample(None, value.contiguous(), None, self.value_mean_std, None, None, None, None, self.exp["next_values"][n], mask=terminated)
+
+    def _rollout_step(self, n, seg):
+        """Rollout step n on the device.  `seg` runs a segment: `call_segment` (eager, and inside the capture of a whole step) or `CapturedRollout.segment` (a graph of its own)."""
+        self._rollout_reset(n)
+        seg("policy", (self.obs,), self._rollout_policy, n)
+        self.obs, rewards, self.dones, infos = self.vec_env.step(self._env_actions if self.clip_actions else self.exp["actions"][n])
+        rewards = rewards.unsqueeze(1) if rewards.dim() == 1 else rewards
+        self.exp["amp_obs"][n].copy_(infos["amp_obs"])   # (eager: the window of the task's AMP strip moves every step)
+        terminate, reward_raw = infos["terminate"], infos["reward_raw"]
+        if self._reward_raw_acc is None:   # the first rollout (also that of a restored checkpoint, whatever its epoch_num) creates the accumulator: eagerly
+            seg = call_segment
+        seg("after", (self.obs, rewards, self.dones, terminate, reward_raw), self._rollout_after, n, rewards, terminate, reward_raw)
+
+    def _rollout_step_torch(self, n):
+        """Rollout step n as torch ops (CPU tensors): the reference's statements (amp_agent.py:315-345)."""
+        e = self.exp
+        self._rollout_reset(n)
+        if self.obs.data_ptr() != e["obses"][n].data_ptr():
+            e["obses"][n].copy_(self.obs)
+        res = self.get_action_values(self.obs)
+        for k in ("values", "neglogpacs", "actions", "mus", "sigmas"):
+            e[k][n].copy_(res[k])
+        self.obs, rewards, self.dones, infos = self.vec_env.step(self.preprocess_actions(res["actions"]))
+        rewards = rewards.unsqueeze(1) if rewards.dim() == 1 else rewards
+        e["amp_obs"][n].copy_(infos["amp_obs"])
+        terminated = self._rollout_bookkeeping(n, rewards, infos["terminate"], infos["reward_raw"])
+        e["next_values"][n].copy_(self._eval_critic(self.obs) * (1.0 - terminated.unsqueeze(-1)))
 
     def play_steps(self):
         self.set_eval()
-        e = self.exp
-        task = self.task
         if self._terminated_flags is None:
             self._terminated_flags = torch.zeros(self.num_actors, device=self.device)
+            self._terminated_mask = torch.zeros(self.num_actors, device=self.device)
             self._env_actions = torch.empty_like(self.exp["actions"][0])
-        terminated_flags = self._terminated_flags.zero_()
+        self._terminated_flags.zero_()
         if self._reward_raw_acc is not None:
             self._reward_raw_acc.zero_()
-        # captured env launches hold the motion library, the parameter struct and the AMP reference table by value / raw pointer: when the task
-        # says any of them moved (resample_motions(), evaluate() swapping libraries, flipped evaluation flags), every captured graph is dropped and
-        # re-captured against the new objects (tests/test_env_gpu.py::test_rollout_graphs_follow_resample_motions_and_evaluate)
-        gen = task.launch_generation() if hasattr(task, "launch_generation") else None
-        if gen != self._roll_generation:
-            if self._roll_graphs:
-                torch.cuda.synchronize()
-                self._roll_graphs.clear()
-                # ... and their memory pool with them (round 5): with every graph of the pool destroyed its use count is zero, and capturing into the
-                # same pool id again trips `use_count > 0` in HIPCachingAllocator unless empty_cache() could free the whole pool -- it cannot while any
-                # tensor allocated during a capture is still referenced (robots: a Unitree H1 run crashed at epoch 101, its first resample_motions())
-                self._roll_pool = None
-            self._roll_generation = gen
-        done_indices = []
-        net = self.model.a2c_network
-        fused = e["obses"].is_cuda
-        graphed = fused and self._rollout_graphs_enabled()
-        vnorm = self.value_mean_std if self.normalize_value else None
-
-        def seg_policy(n):
-            """(A) observation row, policy + value heads, sampling -> row n of the experience buffer."""
-            if self.obs.data_ptr() != e["obses"][n].data_ptr():
-                e["obses"][n].copy_(self.obs)
-            processed = self._preproc_obs(self.obs)
-            with self._autocast():
-                mu, logstd = net.eval_actor(self._actor_obs(self.obs) if self._actor_split else processed)
-                value = net.eval_critic(processed)
-            if self._actor_split:
-                value = value.float()       # (one dtype flag for both heads in phc_policy_sample)
-            policy_sample(mu.contiguous(), value.contiguous(), (logstd[0] if logstd.dim() == 2 else logstd).float().contiguous(), vnorm,
-                          e["actions"][n], e["mus"][n], e["sigmas"][n], e["neglogpacs"][n], e["values"][n])
-            if self.clip_actions:
-                self.preprocess_actions(e["actions"][n], out=self._env_actions)
-
-        def seg_after(n, rewards, terminate, reward_raw):
-            """(B) the step's outputs into row n, next-value critic (zeroed where the episode terminated), episode bookkeeping."""
-            e["next_obses"][n].copy_(self.obs)
-            if self._reward_raw_acc is None:
-                self._reward_raw_acc = torch.zeros(reward_raw.shape[1], dtype=torch.float32, device=self.device)
-            dev_ok = (rewards.is_cuda and rewards.dtype == torch.float32 and rewards.is_contiguous() and self.dones.dtype == torch.int64
-                      and terminate.dtype == torch.int64 and reward_raw.dtype == torch.float32 and reward_raw.is_contiguous() and reward_raw.shape[1] <= 8)
-            if dev_ok:   # rewards / dones / terminated flags / reward means / episode statistics in one launch (phc_rollout_bookkeeping)
-                if self._terminated_mask is None:
-                    self._terminated_mask = torch.zeros(self.num_actors, dtype=torch.float32, device=self.device)
-                terminated = self._terminated_mask
-                L.check(L.load().phc_rollout_bookkeeping(
-                    rewards.data_ptr(), float(self.reward_scale), self.dones.data_ptr(), terminate.data_ptr(), reward_raw.data_ptr(), reward_raw.shape[1],
-                    self.num_actors, e["rewards"][n].data_ptr(), e["dones"][n].data_ptr(), terminated_flags.data_ptr(), terminated.data_ptr(),
-                    self._reward_raw_acc.data_ptr(), self.current_rewards.data_ptr(), self.current_lengths.data_ptr(),
-                    torch.cuda.current_stream().cuda_stream), "phc_rollout_bookkeeping")
-            else:
-                e["rewards"][n].copy_(rewards if self.reward_scale == 1 else rewards * self.reward_scale)
-                e["dones"][n].copy_(self.dones)
-                terminated = terminate.float()
-                terminated_flags.add_(terminated)
-                self._reward_raw_acc.add_(reward_raw.mean(dim=0))
-            with self._autocast():
-                value = net.eval_critic(self._preproc_obs(self.obs))
-            policy_sample(None, value.contiguous(), None, vnorm, None, None, None, None, e["next_values"][n], mask=terminated)
-            if not dev_ok:
-                not_dones = 1.0 - self.dones.float()
-                self.current_rewards.add_(rewards).mul_(not_dones.unsqueeze(1))
-                self.current_lengths.add_(1).mul_(not_dones)
-
-        # ONE hipGraph per rollout step (round 3): reset of the finished envs, observation row, actor / critic / sampling, stepper, post-physics, AMP
-        # window copy, next-value critic and bookkeeping -- ~40 launches -- replayed with a single host call; the task's host-side state (AMP
-        # window position, reset-list slot, info dict) is advanced by task.replay_step_host().  Keyed by the step index and that state; the
-        # start-time draws of the captured reset launch stay fresh through the device-side call counter (phc_im_buffers_t.reset_rng_counter).
-        whole = (graphed and self._reward_raw_acc is not None and getattr(task, "whole_step_capturable", lambda: False)()
-                 and not os.environ.get("PHC_NO_STEP_GRAPH"))
-        if whole:
-            task.align_amp_window()
-
-            def whole_step(n):
-                if n > 0:   # (step 0 resets nothing: see the eager loop below)
-                    task.reset_done()
-                self.obs = task.obs_buf
-                seg_policy(n)
-                self.obs, rewards, self.dones, infos = self.vec_env.step(self._env_actions if self.clip_actions else e["actions"][n])
-                rewards = rewards.unsqueeze(1) if rewards.dim() == 1 else rewards
-                e["amp_obs"][n].copy_(infos["amp_obs"])
-                seg_after(n, rewards, infos["terminate"], infos["reward_raw"])
-
+        roll = self._rollout
+        roll.follow(self.task)
+        if not self.exp["obses"].is_cuda:
             for n in range(self.horizon_length):
-                key = ("step", n) + task.rollout_step_key()
-                if key in self._roll_graphs:
-                    self._roll_graphs[key].replay()
-                    task.replay_step_host(reset=n > 0)
-                else:
-                    self._replay(key, lambda: whole_step(n))   # capture (runs the task's own host bookkeeping), then the first replay: no bookkeeping
-            self.obs, self.dones = task.obs_buf, task.reset_buf
-        for n in range(self.horizon_length if not whole else 0):
-            if self.faithful_reset or not hasattr(task, "reset_done"):
-                self.obs = self.env_reset(done_indices)
-            else:
-                # The reference starts every rollout with `done_indices = []` (amp_agent.py:313): the envs that finished on the LAST step of the previous
-                # rollout are not reset at step 0 -- they run one more step, are flagged again by that step's `_compute_reset` (their clip is still over /
-                # they are still down) and are reset at step 1.  Kept: one in `horizon_length` episode ends carries that extra transition in the reference's
-                # data too (tests/test_learner_epoch.py pins it).
-                if n > 0:
-                    task.reset_done()
-                if np.isfinite(self.vec_env.clip_obs):   # clamp straight into the experience buffer row
-                    self.obs = torch.clamp(task.obs_buf, -self.vec_env.clip_obs, self.vec_env.clip_obs, out=e["obses"][n])
-                else:
-                    self.obs = task.obs_buf
-            if fused:
-                if graphed:
-                    self._replay(("policy", n, self.obs.data_ptr()), lambda: seg_policy(n))
-                else:
-                    seg_policy(n)
-                res = {"actions": self._env_actions if self.clip_actions else e["actions"][n]}
-            else:
-                if self.obs.data_ptr() != e["obses"][n].data_ptr():
-                    e["obses"][n].copy_(self.obs)
-                res = self.get_action_values(self.obs)
-                for k in ("values", "neglogpacs", "actions", "mus", "sigmas"):
-                    e[k][n].copy_(res[k])
-                res = {"actions": self.preprocess_actions(res["actions"])}
-            self.obs, rewards, self.dones, infos = self.vec_env.step(res["actions"])
-            rewards = rewards.unsqueeze(1) if rewards.dim() == 1 else rewards
-            e["amp_obs"][n].copy_(infos["amp_obs"])   # (eager: the window of the task's AMP strip moves every step)
-            if fused:
-                if self._reward_raw_acc is None:       # first rollout: creates the accumulator eagerly
-                    seg_after(n, rewards, infos["terminate"], infos["reward_raw"])
-                elif graphed:
-                    key = ("after", n, self.obs.data_ptr(), rewards.data_ptr(), self.dones.data_ptr(), infos["terminate"].data_ptr(),
-                           infos["reward_raw"].data_ptr())
-                    self._replay(key, lambda: seg_after(n, rewards, infos["terminate"], infos["reward_raw"]))
-                else:
-                    seg_after(n, rewards, infos["terminate"], infos["reward_raw"])
-            else:
-                e["rewards"][n].copy_(rewards if self.reward_scale == 1 else rewards * self.reward_scale)
-                e["next_obses"][n].copy_(self.obs)
-                e["dones"][n].copy_(self.dones)
-                terminated = infos["terminate"].float()
-                terminated_flags += terminated
-                rr = infos["reward_raw"].mean(dim=0)
-                self._reward_raw_acc = rr.clone() if self._reward_raw_acc is None else self._reward_raw_acc.add_(rr)
-                next_vals = self._eval_critic(self.obs)
-                next_vals = next_vals * (1.0 - terminated.unsqueeze(-1))
-                e["next_values"][n].copy_(next_vals)
-                self.current_rewards += rewards
-                self.current_lengths += 1
-                not_dones = 1.0 - self.dones.float()
-                self.current_rewards = self.current_rewards * not_dones.unsqueeze(1)
-                self.current_lengths = self.current_lengths * not_dones
-            if self.faithful_reset or not hasattr(task, "reset_done"):   # (a task without the device-side reset gets the reference's index list)
-                done_indices = self.dones.nonzero(as_tuple=False)[:, 0]
-        reward_raw = self._reward_raw_acc
+                self._rollout_step_torch(n)
+        elif roll.whole_steps():
+            roll.play_whole_steps()
+        else:
+            seg = roll.segment if roll.enabled() else call_segment
+            for n in range(self.horizon_length):
+                self._rollout_step(n, seg)
+        return self._rollout_batch()
+
+    def _rollout_batch(self):
+        """The filled experience buffer as the epoch's batch: discriminator rewards, GAE, [T, N, ...] -> [N * T, ...]."""
+        e = self.exp
         mb_fdones = e["dones"].float()
         amp_rewards = self._calc_amp_rewards(e["amp_obs"])
         mb_rewards = self._combine_rewards(e["rewards"], amp_rewards)
         mb_advs = discount_values(mb_fdones, e["values"], mb_rewards, e["next_values"], self.gamma, self.tau)
-        mb_returns = mb_advs + e["values"]
         batch = {k: swap_and_flatten01(e[k]) for k in ("obses", "rewards", "values", "neglogpacs", "dones", "actions", "mus", "sigmas", "amp_obs")}
-        batch["returns"] = swap_and_flatten01(mb_returns)
-        batch["terminated_flags"] = terminated_flags
-        batch["reward_raw"] = reward_raw / self.horizon_length
+        batch["returns"] = swap_and_flatten01(mb_advs + e["values"])
+        batch["terminated_flags"] = self._terminated_flags
+        batch["reward_raw"] = self._reward_raw_acc / self.horizon_length
         batch["played_frames"] = self.batch_size
         batch["disc_rewards"] = swap_and_flatten01(amp_rewards["disc_rewards"])
         batch["mb_rewards"] = swap_and_flatten01(mb_rewards)
