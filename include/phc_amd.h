@@ -969,6 +969,61 @@ int64_t phc_mse_loss_workspace(void);
 int32_t phc_mse_loss(const void* pred, int32_t is_bf16, const float* target, const int64_t* row_index, int64_t batch, int32_t dim, void* grad, float* loss_out,
                      double* workspace, void* stream);
 
+/* Retargeting fit on the device (csrc/phc_fit.hip, per-lane code csrc/phc_fit.h; an addition to ABI 37, which stays 37): `iterations` trips of the loop of
+ * `fit_clip` (phc_amd/utils/fit_robot_motion.py <- reference scripts/data_process/fit_smpl_motion.py:101-150) for C concatenated clips at once, fp32 throughout.
+ * Clip c owns frames clip_start[c] .. clip_start[c + 1] - 1 (T_c of them); with NB simulated bodies, E extended ones, ND = NB - 1 revolute joints and M matched
+ * bodies one trip is
+ *   1. FK as RobotFK: root rotation = Rodrigues(root_rot[t]) (series branch for |r|^2 < 1e-8), joint j = Rodrigues(axis_j dof[t, j]), extended bodies do not
+ *      rotate, root position = root_trans_offset[t] + root_off[c];
+ *   2. loss_c = mean_{t,m} |p - g| + 0.01 mean_{t,j} dof^2 over the clip's own frames, and its analytic gradient: with u = (p - g) / |p - g| (0 where the
+ *      residual is exactly 0), joint j gets sum_{m in subtree(j)} a_j . ((p_m - p_j) x u_m) / (T_c M) + 0.02 dof_j / (T_c ND) (a_j the joint's axis in the
+ *      world), the root rotation vector J_l(r)^T sum_m (p_m - p_root) x u_m / (T_c M) (J_l the exponential map's left Jacobian, with its series branch),
+ *      root_off[c] sum_t sum_m u / (T_c M);
+ *   3. torch.optim.Adam's step (betas 0.9 / 0.999, eps 1e-8, no weight decay; denom = sqrt(v) / sqrt(1 - b2^k) + eps, step = lr / (1 - b1^k), k = step[c] + 1)
+ *      on dof, root_rot and root_off; step[c] = k;
+ *   4. dof clamped to `range`;
+ *   5. the clamped dof smoothed along time by the normalised 5-tap gaussian (sigma 0.75), replicate-padded at the clip's own two ends.
+ * Two launches per trip on `stream` (plus one per call that lays out the tiles), 256-thread blocks, no atomics: (a) a group of 32 lanes per frame (64 when
+ * NB + E > 32), one lane per body, over tiles of 8 (4) frames that never span two clips: steps 1-4, the clamped dof into `scratch`, one partial sum of the
+ * root_off gradient and of the loss per tile; (b) step 5 from `scratch` into `dof`, and per clip the partial sums added in tile order, root_off's Adam step,
+ * loss[c] and step[c].  Every sum has a fixed order that does not depend on the clip's place in the batch: a clip's state after any number of trips has the
+ * same bits alone, first, last or between other clips, and iterations = a then = b give the bits of a + b.  iterations == 0 checks the arguments and launches
+ * nothing.  phc_fit_scratch_bytes(F, C, NB + E): negative F, C < 1 or NB + E outside [1, PHC_MAX_BODIES]: PHC_EINVAL.
+ * Before any device work, PHC_EINVAL for: a null args or pointer field, num_clips / num_bodies / num_matched / num_frames < 1, num_ext < 0, a NaN lr, iterations < 0, clip_start_host
+ * not starting at 0, not strictly increasing (a clip has at least one frame) or not ending at num_frames, a scratch below phc_fit_scratch_bytes, a pointer not
+ * 4-byte (clip_start: 8-byte; scratch: 16-byte) aligned; PHC_EUNSUPPORTED for num_bodies + num_ext > PHC_MAX_BODIES, num_matched > PHC_FIT_MAX_MATCHED and more than
+ * 2^31 - 1 tiles.  clip_start_host is the caller's host copy of the device array clip_start: the checks and the launch grid read it, the kernels read the
+ * device array.  The contents of the other device arrays are the caller's duty (parents[b] < b with the root alone at -1, match_body in [0, NB + E),
+ * match_slot in [0, M)); whatever they hold, no lane reads or writes outside the arrays' stated sizes. */
+#define PHC_FIT_MAX_MATCHED 32
+typedef struct {
+    int32_t num_bodies, num_ext;              /* NB, E */
+    int32_t num_matched, num_clips;           /* M, C */
+    int64_t num_frames;                       /* F, all clips together */
+    double  lr;                               /* torch.optim.Adam's lr (a python float there) */
+    const int32_t*  parents;                  /* [NB + E]; an extended body's parent is a simulated body */
+    const float*    offsets;                  /* [NB + E, 3] position in the parent's frame */
+    const float*    rest;                     /* [NB + E, 9] rest rotation in the parent's frame, row-major matrices */
+    const float*    axis;                     /* [ND, 3] joint axis of body j + 1 in its own frame */
+    const float*    range;                    /* [ND, 2] lower, upper */
+    const int32_t*  match_body;               /* [M] the matched body */
+    const int32_t*  match_slot;               /* [M] its column of `target` */
+    const uint32_t* subtree;                  /* [NB] bit m: matched entry m lies in the subtree of body j (bit set for match_body[m] == j too) */
+    const int64_t*  clip_start;               /* [C + 1] frame offsets (device) */
+    const int64_t*  clip_start_host;          /* [C + 1] the same values in host memory */
+    const float*    target;                   /* [F, M, 3] */
+    const float*    root_trans_offset;        /* [F, 3] */
+    float *dof, *dof_m, *dof_v;               /* [F, ND] state: parameter, Adam's first and second moment */
+    float *root_rot, *root_rot_m, *root_rot_v;/* [F, 3] */
+    float *root_off, *root_off_m, *root_off_v;/* [C, 3] */
+    int32_t* step;                            /* [C] Adam steps taken */
+    float*   loss;                            /* [C] out: the loss the last trip evaluated (before its step) */
+    void*    scratch;                         /* phc_fit_scratch_bytes(F, C, NB + E) bytes */
+    int64_t  scratch_bytes;
+} phc_fit_args_t;
+int64_t phc_fit_scratch_bytes(int64_t num_frames, int32_t num_clips, int32_t num_bodies_ext);
+int32_t phc_fit_iterate(const phc_fit_args_t* args /* host; pointers device memory except clip_start_host */, int32_t iterations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

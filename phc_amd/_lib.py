@@ -164,6 +164,17 @@ class StreamArgs(C.Structure):
                 ("terminate_buf", c_p), ("track_err", c_p)]
 
 
+FIT_MAX_MATCHED = 32   # PHC_FIT_MAX_MATCHED
+
+
+class FitArgs(C.Structure):
+    _fields_ = [("num_bodies", c_i32), ("num_ext", c_i32), ("num_matched", c_i32), ("num_clips", c_i32), ("num_frames", c_i64), ("lr", C.c_double),
+                ("parents", c_p), ("offsets", c_p), ("rest", c_p), ("axis", c_p), ("range", c_p), ("match_body", c_p), ("match_slot", c_p), ("subtree", c_p),
+                ("clip_start", c_p), ("clip_start_host", c_p), ("target", c_p), ("root_trans_offset", c_p), ("dof", c_p), ("dof_m", c_p), ("dof_v", c_p),
+                ("root_rot", c_p), ("root_rot_m", c_p), ("root_rot_v", c_p), ("root_off", c_p), ("root_off_m", c_p), ("root_off_v", c_p), ("step", c_p),
+                ("loss", c_p), ("scratch", c_p), ("scratch_bytes", c_i64)]
+
+
 class RecordArgs(C.Structure):
     _fields_ = [("num_envs", c_i32), ("obs_dim", c_i32), ("num_actions", c_i32), ("step", c_i32), ("capacity", c_i64), ("obs_buf", c_p), ("obs_prev", c_p),
                 ("clean_actions", c_p), ("actions", c_p), ("reset_buf", c_p), ("rows", c_p), ("row_start", c_p), ("obs", c_p), ("clean", c_p), ("env", c_p),
@@ -234,6 +245,8 @@ _OPTIONAL_SIGNATURES = {
     "phc_colsum_silu_bf16": ([c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p], c_i32),
     "phc_mse_loss_workspace": ([], c_i64),
     "phc_mse_loss": ([c_p, c_i32, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p], c_i32),
+    "phc_fit_scratch_bytes": ([c_i64, c_i32, c_i32], c_i64),
+    "phc_fit_iterate": ([P(FitArgs), c_i32, c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

@@ -159,6 +159,23 @@ def clip_args_struct(num_clips, num_frames, num_bodies, num_trees, parents, loca
     return a
 
 
+FIT_ARRAYS = ("parents", "offsets", "rest", "axis", "range", "match_body", "match_slot", "subtree", "clip_start", "clip_start_host", "target",
+              "root_trans_offset", "dof", "dof_m", "dof_v", "root_rot", "root_rot_m", "root_rot_v", "root_off", "root_off_m", "root_off_v", "step", "loss")
+
+
+def fit_args_struct(num_bodies, num_ext, num_matched, num_clips, num_frames, lr, scratch, scratch_bytes, **arrays):
+    """phc_fit_args_t (phc_fit_iterate): `arrays` holds every name of FIT_ARRAYS as a torch tensor / numpy array or a raw address; clip_start_host is host memory."""
+    assert set(arrays) == set(FIT_ARRAYS), sorted(set(arrays) ^ set(FIT_ARRAYS))
+    a = L.FitArgs()
+    a.num_bodies, a.num_ext, a.num_matched, a.num_clips, a.num_frames = int(num_bodies), int(num_ext), int(num_matched), int(num_clips), int(num_frames)
+    a.lr = float(lr)
+    addr = lambda x: x if x is None or isinstance(x, int) else ptr(x)
+    for k in FIT_ARRAYS:
+        setattr(a, k, addr(arrays[k]))
+    a.scratch, a.scratch_bytes = addr(scratch), int(scratch_bytes)
+    return a
+
+
 def im_params_struct(dt, max_episode_length, reward_specs, power_reward, power_coefficient, enable_early_termination,
                      use_mean_termination, disable_collision_check, local_root_obs, root_height_obs, num_track_bodies,
                      track_slot, reset_mask, num_reset_bodies, first_reset_body, termination_distances, num_key_bodies, key_body_ids,

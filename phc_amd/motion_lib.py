@@ -853,7 +853,8 @@ class MotionLibReal(MotionLibBase):
     """Robot motion library (reference phc/utils/motion_lib_real.py:54-430): clips are `pose_aa` per body + root translation;
     FK is `Humanoid_Batch.fk_batch` (restated in `process_clip_real`); joint coordinates are stored and blended as scalars;
     the `extend_config` bodies (hands / head) exist in the reference only.  No heading randomisation (commented out in the
-    reference, :395-404).  `cfg.robot_model` is the compiled articulation (phc_amd.model), `cfg.robot` the robot yaml."""
+    reference, :395-404).  `cfg.robot_model` is the compiled articulation (phc_amd.model), `cfg.robot` the robot yaml.
+    Its clips come from `phc_amd.utils.fit_robot_motion.fit_clips` (the retargeting fit, on the host or in HIP: DESIGN.md §4.11)."""
 
     dofs_per_joint = 1
 
