@@ -708,6 +708,62 @@ typedef struct {
 } phc_push_args_t;
 int32_t phc_push_advance(const phc_push_args_t* args /* host */, void* stream);
 
+/* The getup task's episode draws on the device (csrc/phc_getup.hip, per-env code and the rules in full csrc/phc_getup.h; additions to ABI 37, which stays 37):
+ * `+env.task_rng=device`.  phc_getup_assign is the device form of HumanoidImGetup._reset_envs(reset_buf.nonzero()) up to the reset launches -- same rules as
+ * humanoid_im_getup.py:131-196, its own numbers.  For every env i with reset_buf[i] != 0:
+ *   release   avail[assign[i]] = 0 (an env that never held a fall state has assign[i] == 0 and releases slot 0, as the reference does; an assign[i] outside
+ *             [0, N) releases nothing);
+ *   draw      u[0..1] = getup_draws(key, env_offset + i, k[i]); k[i] += 1;
+ *   decide    kind[i] = 2 (RECOVERY) when u[0] < prob[0] and terminate_buf[i] == 1, else 3 (FALL) when u[1] < prob[1], else 1 (NORMAL); 0 for an env not done;
+ *   slots     FALL env of rank r (env order) takes pick = free[pi(r)], free[0 .. F) = the slots with avail == 0 after all releases, in slot order, pi a keyed
+ *             bijection of [0, F) (cycle-walking four-round Feistel network) that depends on (key, *launch_count, F) alone; *launch_count += 1 per launch.
+ *             FALL envs of rank >= F (impossible while every held slot has one holder) become NORMAL;
+ *   teleport  root_states[i] = fall_root[pick], dof_state[i, :, 0] = fall_dof_pos[pick], dof_state[i, :, 1] = 0; avail[pick] = 1, assign[i] = pick;
+ *   counters  recovery_counter[i] = recovery_steps for FALL and RECOVERY envs;
+ *   publish   normal_flag[i] = kind[i] == 1; fall_list[0 .. n_f) = the FALL envs in env order, every other entry N.
+ * One workgroup of 1024 threads, block scans over tiles of 1024 envs, no atomics: the result is a function of (key, counters, inputs) alone and bit-equal to the
+ * host build of phc_getup.h.  All lanes read *launch_count before the first barrier of the launch, lane 0 writes it after the last.
+ * PHC_EINVAL before any device work for: a null args or any null pointer in it (prob included), num_envs < 0, num_dof < 1, recovery_steps < 0, env_offset < 0 or
+ * env_offset + num_envs > 2^32.  PHC_EUNSUPPORTED: num_envs > 2^20.  num_envs == 0 returns 0 without a launch.  No lane reads or writes outside the stated sizes
+ * whatever the device arrays hold. */
+typedef struct {
+    int32_t num_envs, num_dof;                /* N (envs == fall-state slots), D */
+    int32_t recovery_steps;
+    int32_t reserved;
+    uint64_t key;                             /* stream key (the caller folds its seed into it) */
+    int64_t env_offset;                       /* global index of env 0 */
+    const float* prob;                        /* device [2]: p_recovery, p_fall */
+    const int64_t* reset_buf;                 /* [N] */
+    const int64_t* terminate_buf;             /* [N] */
+    const float* fall_root;                   /* [N, 13] */
+    const float* fall_dof_pos;                /* [N, D] */
+    float* root_states;                       /* [N, 13] */
+    float* dof_state;                         /* [N, D, 2] */
+    int64_t* avail;                           /* [N] 1 = the slot is held */
+    int64_t* assign;                          /* [N] the slot env i took last */
+    int32_t* recovery_counter;                /* [N] phc_im_buffers_t.recovery_counter */
+    int32_t* k;                               /* [N] draws this env has made */
+    int64_t* launch_count;                    /* [1] launches so far (the permutation's counter) */
+    int32_t* kind;                            /* [N] out */
+    int64_t* normal_flag;                     /* [N] out */
+    int64_t* fall_list;                       /* [N] out */
+    int32_t* free_list;                       /* [N] scratch */
+} phc_getup_args_t;
+int32_t phc_getup_assign(const phc_getup_args_t* args /* host */, void* stream);
+
+/* The resets behind phc_getup_assign, masked instead of listed.
+ * phc_refresh_body_state_masked: phc_refresh_body_state_indexed over `fall_list` [num_envs] in DEVICE memory whose entries are env ids or num_envs (= skip this
+ *   slot): the list phc_getup_assign publishes, so the stepper's kernel is launched as it is, over num_envs slots.  The caller guarantees 0 <= entry <= num_envs.
+ * phc_im_reset_from_state_masked: phc_im_reset_from_state for the envs with kind[i] == 3 (fill_history = 1) and kind[i] == 2 (fill_history = 0), the same
+ *   per-lane code; every other env is untouched.  PHC_EINVAL for a null `kind`, otherwise the checks of phc_im_reset_from_state. */
+int32_t phc_refresh_body_state_masked(const phc_model_t* model, const phc_sim_state_t* sim, const int64_t* fall_list, void* stream);
+int32_t phc_im_reset_from_state_masked(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
+                                       const phc_im_buffers_t* buf, const int32_t* kind, void* stream);
+
+/* The per-step uniforms of cycle_motion / far starts (csrc/phc_getup.hip): one lane per env, u[0..2] = task_draws(key, env_offset + i, k[i]) -> cycle_phase[i],
+ * offset_rand[i, 0..1] (each nullable), k[i] += 1 for EVERY env.  PHC_EINVAL: num_envs < 0, a null k, env_offset < 0 or env_offset + num_envs > 2^32. */
+int32_t phc_task_draws(int32_t num_envs, uint64_t key, int64_t env_offset, int32_t* k, float* cycle_phase /*[N]*/, float* offset_rand /*[N, 2]*/, void* stream);
+
 /* Domain randomisation in the stepper (csrc/phc_sim_dr.hip, the DR instantiations of the stepper's kernel; per-lane code csrc/phc_dr.h; additions to ABI 37, which
  * stays 37): phc_sim_step with PER-ENV physics.  With `dr` NULL, or both of its tensors NULL, and a model phc_sim_step accepts, the call IS phc_sim_step: same
  * checks, same launch, same bits.

@@ -118,6 +118,13 @@ class PushArgs(C.Structure):
                 ("progress_buf", c_p), ("remaining", c_p), ("countdown", c_p), ("body", c_p), ("k", c_p), ("started", c_p), ("force", c_p)]
 
 
+class GetupArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_dof", c_i32), ("recovery_steps", c_i32), ("reserved", c_i32), ("key", C.c_uint64), ("env_offset", c_i64),
+                ("prob", c_p), ("reset_buf", c_p), ("terminate_buf", c_p), ("fall_root", c_p), ("fall_dof_pos", c_p), ("root_states", c_p), ("dof_state", c_p),
+                ("avail", c_p), ("assign", c_p), ("recovery_counter", c_p), ("k", c_p), ("launch_count", c_p), ("kind", c_p), ("normal_flag", c_p),
+                ("fall_list", c_p), ("free_list", c_p)]
+
+
 P = C.POINTER
 class SimDr(C.Structure):
     _fields_ = [("env_friction", c_p), ("torque_noise", c_p), ("k", c_p), ("key", C.c_uint64), ("env_offset", c_i64)]
@@ -247,6 +254,10 @@ _OPTIONAL_SIGNATURES = {
     "phc_mse_loss": ([c_p, c_i32, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p], c_i32),
     "phc_fit_scratch_bytes": ([c_i64, c_i32, c_i32], c_i64),
     "phc_fit_iterate": ([P(FitArgs), c_i32, c_p], c_i32),
+    "phc_getup_assign": ([P(GetupArgs), c_p], c_i32),
+    "phc_refresh_body_state_masked": ([P(Model), P(SimState), c_p, c_p], c_i32),
+    "phc_im_reset_from_state_masked": ([P(Model), P(MotionLib), P(ImParams), P(SimState), P(ImBuffers), c_p, c_p], c_i32),
+    "phc_task_draws": ([c_i32, C.c_uint64, c_i64, c_p, c_p, c_p, c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

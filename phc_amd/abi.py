@@ -176,6 +176,24 @@ def fit_args_struct(num_bodies, num_ext, num_matched, num_clips, num_frames, lr,
     return a
 
 
+GETUP_ARRAYS = ("prob", "reset_buf", "terminate_buf", "fall_root", "fall_dof_pos", "root_states", "dof_state", "avail", "assign", "recovery_counter", "k",
+                "launch_count", "kind", "normal_flag", "fall_list", "free_list")
+GETUP_MAX_ENVS = 1 << 20   # GETUP_MAX_ENVS (csrc/phc_getup.h): PHC_EUNSUPPORTED above
+GETUP_BLOCK = 1024         # GETUP_BLOCK: envs per scan tile
+
+
+def getup_args_struct(num_envs, num_dof, key, env_offset=0, recovery_steps=0, **arrays):
+    """phc_getup_args_t (phc_getup_assign): `arrays` holds every name of GETUP_ARRAYS as a torch tensor / numpy array, a raw address or None."""
+    assert set(arrays) == set(GETUP_ARRAYS), sorted(set(arrays) ^ set(GETUP_ARRAYS))
+    a = L.GetupArgs()
+    a.num_envs, a.num_dof, a.recovery_steps, a.reserved = int(num_envs), int(num_dof), int(recovery_steps), 0
+    a.key, a.env_offset = int(key), int(env_offset)
+    for k in GETUP_ARRAYS:
+        x = arrays[k]
+        setattr(a, k, x if x is None or isinstance(x, int) else ptr(x))
+    return a
+
+
 def im_params_struct(dt, max_episode_length, reward_specs, power_reward, power_coefficient, enable_early_termination,
                      use_mean_termination, disable_collision_check, local_root_obs, root_height_obs, num_track_bodies,
                      track_slot, reset_mask, num_reset_bodies, first_reset_body, termination_distances, num_key_bodies, key_body_ids,

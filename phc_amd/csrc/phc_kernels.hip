@@ -49,6 +49,18 @@ __global__ __launch_bounds__(256) void k_im_reset_from_state(phc_model_t model, 
     im_reset_from_state_lane(model, lib, prm, sim, buf, env_ids[r], lane, fill_history);
 }
 
+// ... and the same for the envs phc_getup_assign marked (kind 3 = FALL: history filled, kind 2 = RECOVERY: history kept): one lane group per env, masked.
+template <int G>
+__global__ __launch_bounds__(256) void k_im_reset_from_state_masked(phc_model_t model, phc_motion_lib_t lib, phc_im_params_t prm, phc_sim_state_t sim,
+                                                                   phc_im_buffers_t buf, const int32_t* __restrict__ kind) {
+    const int lane = threadIdx.x & (G - 1);
+    const int64_t env = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    if (env >= sim.num_envs) return;
+    const int kd = kind[env];
+    if (kd != 2 && kd != 3) return;
+    im_reset_from_state_lane(model, lib, prm, sim, buf, env, lane, kd == 3);
+}
+
 #ifdef PHC_SIM_PROFILE   // one lane group's timeline through the reset kernel (scripts/probes/reset_timeline.py; the product library has none of this)
 extern "C" int32_t phc_debug_reset_timeline(unsigned long long* out64, int32_t group) {
     if (out64 && hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_phc_rtl), sizeof(g_phc_rtl)) != hipSuccess) return -1;
@@ -265,6 +277,17 @@ int32_t phc_im_reset_from_state(const phc_model_t* model, const phc_motion_lib_t
     return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), false, [&](auto, auto g, auto) {
         hipLaunchKernelGGL(k_im_reset_from_state<g()>, dim3(env_blocks(num_reset, g())), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim, *buf,
                            num_reset, env_ids, fill_history);
+    });
+}
+
+int32_t phc_im_reset_from_state_masked(const phc_model_t* model, const phc_motion_lib_t* lib, const phc_im_params_t* prm, const phc_sim_state_t* sim,
+                                       const phc_im_buffers_t* buf, const int32_t* kind, void* stream) {
+    if (int32_t rc = check_im_reset_from_state(model, lib, prm, sim, buf, 0, nullptr); rc) return rc;
+    if (!kind || sim->num_envs < 0) return PHC_EINVAL;
+    if (sim->num_envs == 0) return 0;
+    return task_launch(prm->dofs_per_joint == 1, group_lanes(model->num_bodies, prm->num_ext_bodies), false, [&](auto, auto g, auto) {
+        hipLaunchKernelGGL(k_im_reset_from_state_masked<g()>, dim3(env_blocks(sim->num_envs, g())), dim3(256), 0, (hipStream_t)stream, *model, *lib, *prm, *sim,
+                           *buf, kind);
     });
 }
 

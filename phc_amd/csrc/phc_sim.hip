@@ -110,4 +110,16 @@ int32_t phc_refresh_body_state_indexed(const phc_model_t* model, const phc_sim_s
     return launch_status();
 }
 
+// the same launch over num_envs slots of a device list whose entries are env ids or num_envs: the kernel idles a slot whose env is not below num_envs
+int32_t phc_refresh_body_state_masked(const phc_model_t* model, const phc_sim_state_t* sim, const int64_t* fall_list, void* stream) {
+    int32_t rc = check_model(model);
+    if (rc) return rc;
+    if (!sim || sim->num_envs < 0 || !fall_list) return PHC_EINVAL;
+    if (sim->num_envs == 0) return 0;
+    phc_sim_params_t prm = {};
+    prm.substeps = 1;
+    sim_launch<false, false>(model, prm, sim, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, fall_list, sim->num_envs, WrenchArgs<false>());
+    return launch_status();
+}
+
 }  // extern "C"

@@ -58,6 +58,16 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+TASK_DRAWS_TAG = 0x7461736B64726177   # ("taskdraw") stream tags of env.task_rng=device (perturb.stream_key)
+GETUP_DRAWS_TAG = 0x6765747570647277  # ("getupdrw")
+
+
+def launches_only(fn):
+    """Marks a `step` override that is launches and host bookkeeping only: `whole_step_capturable()` admits the base step and the marked ones."""
+    fn.launches_only = True
+    return fn
+
+
 class HumanoidIm:
 
     class StateInit(Enum):  # humanoid_amp.py:73-78
@@ -532,6 +542,12 @@ class HumanoidIm:
     # ---- host phase: options of HumanoidAMP / HumanoidIm (humanoid_amp.py:109-136, humanoid_im.py:71-123) ----
     def _setup_im_options(self):
         env = self.cfg["env"]
+        # env.task_rng: who makes the task's own random draws during a rollout step.  `torch` (default): torch's generators on the host side, as ever.
+        # `device`: counter-based hashes inside HIP launches (phc_task_draws here, phc_getup_assign in HumanoidImGetup) -- same rules, other numbers, and
+        # nothing between the launches that a stream capture could not hold
+        self.task_rng = str(env.get("task_rng", "torch"))
+        if self.task_rng not in ("torch", "device"):
+            raise ValueError(f"env.task_rng={self.task_rng!r}: 'torch' or 'device'")
         # draws behind the random reference offsets of zero_out_far_train (reset, clip restart) / cycle_motion_xp (clip restart)
         self._far_start = bool(self.zero_out_far and self.zero_out_far_train)
         if self.zero_out_far and self._track_bodies[0] != self._body_names[0]:
@@ -573,6 +589,15 @@ class HumanoidIm:
         self._cycle_phase = torch.zeros(N, **f32) if self.cycle_motion else None
         self._offset_rand = torch.zeros((N, 2), **f32) if (self._far_start or (self.cycle_motion and self.cycle_motion_xp)) else None
         self._recovery_counter = None                            # HumanoidImGetup extends this phase with one
+        # env.task_rng=device: the stream of phc_task_draws -- keyed from the run's seed plus a tag like the push schedule's (perturb.stream_key), so switching
+        # it on leaves every other stream of the run as it was; the ranks of one run draw disjoint streams through env_offset; one draw counter per env
+        self._task_draw_k = None
+        if self.task_rng == "device":
+            from ...perturb import stream_key
+            self._task_seed = int(self.cfg.get("seed", 0))
+            self._task_env_offset = int(self.cfg.get("rank", os.environ.get("RANK", 0))) * N
+            self._task_draw_key = stream_key(self._task_seed, TASK_DRAWS_TAG)
+            self._task_draw_k = torch.zeros(N, device=dev, dtype=torch.int32)
         S, A = self._num_amp_obs_steps, self._num_amp_obs_per_step
         # AMP history (humanoid_amp.py:125-131): every env owns a strip of 2 S frames; the history is the window of S frames starting at
         # row `_amp_head` (newest first, like `_amp_obs_buf` of the reference).  A step writes its frame in the row BEFORE the window and
@@ -804,6 +829,7 @@ class HumanoidIm:
                                       limb_weights=self.humanoid_limb_and_weights.cpu(), **how)
 
     # ------------------------------------------------------------------ step (base_task.py:216-234)
+    @launches_only
     def step(self, actions):
         self.pre_physics_step(actions)
         ev = self._launch_events    # bench.py: (stepper pair, post-physics pair) of HIP events for THIS step, or None (consumed)
@@ -912,9 +938,12 @@ class HumanoidIm:
         if self.cycle_motion:
             # the draw behind `_sample_time` of the envs whose clip restarts this step (humanoid_im.py:1127); one value per
             # env is drawn (the reference draws only as many as restart, so the RNG streams differ in length, not in law)
-            torch.rand(self.num_envs, out=self._cycle_phase)
-            if self._offset_rand is not None:
-                torch.rand(self._offset_rand.shape, out=self._offset_rand)
+            if self.task_rng == "device":
+                self._task_draws(self._cycle_phase, self._offset_rand)
+            else:
+                torch.rand(self.num_envs, out=self._cycle_phase)
+                if self._offset_rand is not None:
+                    torch.rand(self._offset_rand.shape, out=self._offset_rand)
         if self._use_reset_list and self._reset_list_pending:   # the previous step's list was never consumed (reset(env_ids) idiom): start this one empty
             self._reset_count[self._reset_slot].zero_()
         self._refresh_hist_obs()
@@ -1009,7 +1038,16 @@ class HumanoidIm:
         state = {"reset_rng_counter": int(self._reset_rng_dev.item()), "reset_counter": int(self._reset_counter)}
         if hasattr(self._push, "state_dict"):   # `+perturb.rng=device`: a resumed run continues its pushes
             state["push_schedule"] = self._push.state_dict()
+        if self.task_rng == "device":           # `+env.task_rng=device`: ... and the task's own draws
+            state["task_rng"] = self._task_rng_state()
         return state
+
+    def _task_rng_state(self):
+        """The counters of the task's device draws as host tensors (HumanoidImGetup adds its own)."""
+        return {"draw_k": self._task_draw_k.cpu()}
+
+    def _load_task_rng_state(self, saved):
+        self._task_draw_k.copy_(saved["draw_k"])
 
     def set_env_rng_state(self, state):
         self._reset_rng_dev.fill_(int(state.get("reset_rng_counter", 0)))
@@ -1023,14 +1061,31 @@ class HumanoidIm:
             else:
                 print(f"[phc_amd] push schedule state not restored: the checkpoint's is for {tuple(saved['state'].shape)[-1]} envs, this task has "
                       f"{self.num_envs}; the schedule starts afresh", flush=True)
+        # the task's device draws: under the same rule (same num_envs, not in test mode)
+        saved = state.get("task_rng")
+        if saved is not None and self.task_rng == "device" and not flags.test:
+            if tuple(saved["draw_k"].shape) == (self.num_envs,):
+                self._load_task_rng_state(saved)
+            else:
+                print(f"[phc_amd] task draw counters not restored: the checkpoint's are for {tuple(saved['draw_k'].shape)[-1]} envs, this task has "
+                      f"{self.num_envs}; the draws start afresh", flush=True)
 
     def whole_step_capturable(self):
         """True when reset_done() + step() consist of launches and host bookkeeping only (no host-side random draws or syncs between them), so that
         the learner may capture them, with its own policy / critic segments, into ONE hipGraph per rollout step."""
-        return bool(self._use_reset_list and not (self.cycle_motion or self._far_start or self._occl_training or self.add_obs_noise or self._fut_tracks_dropout
-                                                  or self.collect_dataset or self.obs_v == 5 or self._hist_obs_cols or flags.im_eval or flags.test)
-                    and type(self).step is HumanoidIm.step and type(self).reset_done is HumanoidIm.reset_done
+        # the draws of cycle_motion / far starts block a capture only while torch makes them (env.task_rng=torch): phc_task_draws is a launch.
+        # step / reset_done: the base class's, or an override known to be launches (and torch modules on device tensors) only -- marked `launches_only`:
+        # MCPMixin.step is compose_actions (frozen torch modules under no_grad, no host read) plus the base step's three calls; HumanoidImGetup.reset_done in
+        # device mode is four launches (`_reset_done_capturable`)
+        host_draws = (self.cycle_motion or self._far_start) and self.task_rng != "device"
+        return bool(self._reset_done_capturable() and not (host_draws or self._occl_training or self.add_obs_noise or self._fut_tracks_dropout
+                                                           or self.collect_dataset or self.obs_v == 5 or self._hist_obs_cols or flags.im_eval or flags.test)
+                    and getattr(type(self).step, "launches_only", False)
                     and type(self).post_physics_step is HumanoidIm.post_physics_step and type(self).pre_physics_step is HumanoidIm.pre_physics_step)
+
+    def _reset_done_capturable(self):
+        """Is this task's reset_done() launches and host bookkeeping only?  The base class's is, on its device-built list."""
+        return self._use_reset_list and type(self).reset_done is HumanoidIm.reset_done
 
     def rollout_step_key(self):
         """What a captured rollout step depends on besides the step index: the reset-list slot and whether a list is pending (the AMP window position
@@ -1115,12 +1170,20 @@ class HumanoidIm:
         """In front of every reset launch: the far-start draw and the AMP reference table (not for a reset from the env's own state, which reads
         neither), the history columns of the observation; -> the launch's buffers, AMP history written in place."""
         if self._far_start and not from_state:
-            torch.rand(self._offset_rand.shape, out=self._offset_rand)
+            if self.task_rng == "device":
+                self._task_draws(None, self._offset_rand)
+            else:
+                torch.rand(self._offset_rand.shape, out=self._offset_rand)
         self._refresh_hist_obs()
         if not from_state:
             self._ensure_amp_ref_table()
         cur = self._amp_obs_buf
         return self._buffers(cur, cur)
+
+    def _task_draws(self, cycle_phase, offset_rand):
+        """env.task_rng=device: U[0, 1) into `cycle_phase` [N] and / or `offset_rand` [N, 2] as one launch; every env's draw counter moves on."""
+        L.check(self._lib.phc_task_draws(self.num_envs, self._task_draw_key, self._task_env_offset, self._task_draw_k.data_ptr(), abi.ptr(cycle_phase),
+                                         abi.ptr(offset_rand), _stream()), "phc_task_draws")
 
     def _refresh_hist_obs(self):
         """env.enableHistObs: the current AMP history (the one the launch about to be issued has not touched yet) into the trailing columns of

@@ -7,7 +7,7 @@ pre-physics / physics / post-physics launches.  The PNN forward is `num_prim` sm
 import torch
 
 from ...learning.network import PNN
-from .humanoid_im import HumanoidIm
+from .humanoid_im import HumanoidIm, launches_only
 
 
 def load_pnn(checkpoint, num_prim, has_lateral, activation="relu", device="cpu"):
@@ -166,6 +166,7 @@ class MCPMixin:
                 acts = [net(obs) for net in self.actors]      # humanoid_im_mcp.py:78-79
             return torch.sum(weights[:, :, None] * torch.stack(acts, dim=1), dim=1)
 
+    @launches_only   # (torch modules on device tensors under no_grad and the base step's three calls: nothing a stream capture cannot hold)
     def step(self, weights):
         actions = self.compose_actions(weights.to(self.device))
         self.pre_physics_step(actions)

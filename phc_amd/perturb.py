@@ -134,10 +134,11 @@ def _splitmix64(z):
     return z ^ (z >> 31)
 
 
-def stream_key(seed):
+def stream_key(seed, tag=0x7075736873636864):   # ("pushschd")
     """The 64-bit stream key of a device schedule.  The tag keeps it apart from the key the reset launch derives from the same run seed for its
-    start-time draws (phc_im_reset_done: splitmix64(splitmix64(seed) ^ counter * odd constant))."""
-    return _splitmix64(_splitmix64(int(seed) & ((1 << 64) - 1)) ^ 0x7075736873636864)   # ("pushschd")
+    start-time draws (phc_im_reset_done: splitmix64(splitmix64(seed) ^ counter * odd constant)), and the streams of one run apart from each other: the
+    push schedule's is the default, the task's own draws (`+env.task_rng=device`) pass theirs."""
+    return _splitmix64(_splitmix64(int(seed) & ((1 << 64) - 1)) ^ int(tag))
 
 
 class DevicePushSchedule(_Schedule):
