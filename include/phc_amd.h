@@ -851,6 +851,49 @@ typedef struct {
 int64_t phc_clip_scratch_bytes(int64_t num_frames, int32_t num_bodies);
 int32_t phc_clip_process(const phc_clip_args_t* args /* host; all pointers device memory */, void* stream);
 
+/* Clip processing on the device for the robots (csrc/phc_clip_real.hip, per-lane code csrc/phc_clip_real.h; an addition to ABI 37, which stays 37): the robot
+ * branch of `_run_clip_job` of phc_amd/motion_lib.py for U concatenated clips of one all-revolute model with NB simulated and E extended bodies -- the height
+ * fix, `Humanoid_Batch`'s matrix forward kinematics (`robot_fk`: axis-angle -> quaternion -> matrix per body, wmat = wmat_parent (rest_mat pm), the best-
+ * conditioned of the four matrix -> quaternion candidates taken as is), np.gradient and finite-difference angular velocities with the gaussian filter of
+ * phc_clip_process, dof_pos as the row sum of pose_aa, dvs as its finite difference (the clip's LAST frame takes the difference of frames T-3 and T-2, as the
+ * reference does) -- in fp64, rounded once to the fp32 records of phc_motion_lib_t (revolute layout: gts 3(NB+E) | grs 4(NB+E) | gvs 3NB | gavs 3NB |
+ * dof_pos NB-1 | dvs NB-1 | pad floats written as 0).  Launches on `stream`, 256-thread blocks:
+ *   0. (fix_height != 0 only) one block per clip: the FK of the clip's first frame, z = wpos_z + wmat[2, :] . contact_pos - contact_radius over the C contact
+ *      points, clip_dz[c] = their minimum into `scratch`; the root translation of every frame of the clip is lowered by it;
+ *   1. one lane per (frame, body in NB+E) over tiles of up to 16 frames: the lane walks its own ancestor chain from the root, for frame f and (simulated
+ *      bodies, for the angular velocity) for frame f + 1; positions, rotations, dof_pos and dvs go through an LDS image of the tile's records to coalesced
+ *      stores; the fp64 positions and raw angular velocities of the NB simulated bodies go to `scratch`, and one lane per frame records the frame's clip there;
+ *   2. one lane per velocity float of a record (6 NB, at column 7 (NB+E)): the 17-tap filter over the scratch rows of the lane's clip.
+ * No lane loops over a clip's frames.  phc_clip_real_scratch_bytes(F, NB, E, U) = 48 F NB + 8 U + 4 F rounded up to 8 (F < 0, NB < 1, E < 0, U < 1: PHC_EINVAL).
+ * Before any device work, PHC_EINVAL for: a null args or pointer field (the three contact arrays only with fix_height), num_clips / num_bodies < 1,
+ * num_ext < 0, num_contacts < 1 with fix_height, num_frames < 3 num_clips, frame_stride != the revolute record's, scratch_bytes below
+ * phc_clip_real_scratch_bytes, an f64 / i64 array or the scratch not 8-byte aligned, an i32 / f32 array not 4-byte aligned; PHC_EUNSUPPORTED for
+ * num_bodies + num_ext > PHC_MAX_BODIES and for a num_frames that does not fit the launch grids (6 num_bodies num_frames > (2^31 - 1) 256, or more than 2^31 - 1 tiles).
+ * The contents of the device arrays are the caller's duty (phc_amd/motion_lib.py validates them before the upload): clips of at least 3 frames, clip_start
+ * ascending from 0 to num_frames, parents[j] < j with exactly the entries < 0 as roots, contact_body in [0, NB).  Whatever they hold, no lane reads or
+ * writes outside the arrays' stated sizes. */
+typedef struct {
+    int32_t num_clips, num_bodies, num_ext, num_contacts; /* U, NB, E, C */
+    int32_t frame_stride;                     /* floats per record: 7 (NB+E) + 6 NB + 2 (NB-1) rounded up to a multiple of 4 */
+    int32_t fix_height;                       /* 0: no height fix (launch 0 is skipped, the contact arrays are not read) */
+    int64_t num_frames;                       /* F, all clips together */
+    const int32_t* parents;                   /* [NB+E] the extended bodies appended */
+    const double*  offsets;                   /* [NB+E, 3] translation to the parent */
+    const double*  rest_mat;                  /* [NB+E, 3, 3] rest rotations, row-major matrices */
+    const double*  pose_aa;                   /* [F, NB+E, 3] axis-angle per body */
+    const double*  trans;                     /* [F, 3] root translation */
+    const int64_t* clip_start;                /* [U + 1] frame offsets; the last entry is F */
+    const double*  clip_dt;                   /* [U] 1 / fps */
+    const int32_t* contact_body;              /* [C] */
+    const double*  contact_pos;               /* [C, 3] in the body's frame */
+    const double*  contact_radius;            /* [C] */
+    void*          scratch;                   /* phc_clip_real_scratch_bytes(F, NB, E, U) bytes */
+    int64_t        scratch_bytes;
+    float*         frames;                    /* [F, frame_stride] out */
+} phc_clip_real_args_t;
+int64_t phc_clip_real_scratch_bytes(int64_t num_frames, int32_t num_bodies, int32_t num_ext, int32_t num_clips);
+int32_t phc_clip_process_real(const phc_clip_real_args_t* args /* host; all pointers device memory */, void* stream);
+
 /* HumanoidTeleop's regularisation rewards and its recovery window after a velocity push (csrc/phc_teleop.hip, per-env code csrc/phc_teleop.h; an addition to
  * ABI 37, which stays 37; reference: phc/env/tasks/humanoid_teleop.py:95-101,167-307).  One launch per env step AFTER phc_im_post_physics on the same stream;
  * a group of 32 lanes per env, lanes along a DoF row, 256-thread blocks; every sum is a fixed-order butterfly over the group (no atomics): the same inputs

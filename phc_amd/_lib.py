@@ -142,6 +142,13 @@ class ClipArgs(C.Structure):
                 ("scratch_bytes", c_i64), ("frames", c_p)]
 
 
+class ClipRealArgs(C.Structure):
+    _fields_ = [("num_clips", c_i32), ("num_bodies", c_i32), ("num_ext", c_i32), ("num_contacts", c_i32), ("frame_stride", c_i32), ("fix_height", c_i32),
+                ("num_frames", c_i64), ("parents", c_p), ("offsets", c_p), ("rest_mat", c_p), ("pose_aa", c_p), ("trans", c_p), ("clip_start", c_p),
+                ("clip_dt", c_p), ("contact_body", c_p), ("contact_pos", c_p), ("contact_radius", c_p), ("scratch", c_p), ("scratch_bytes", c_i64),
+                ("frames", c_p)]
+
+
 TELEOP_TERMS = ("dof_pos_limits", "torque_limits", "torques", "dof_vel", "dof_acc", "action_rate", "slippage", "feet_contact_forces", "stumble",
                 "feet_air_time_teleop", "feet_ori")   # PHC_TELEOP_*: the bit of each term
 TELEOP_MAX_FEET = 8   # PHC_TELEOP_MAX_FEET
@@ -245,6 +252,8 @@ _OPTIONAL_SIGNATURES = {
     "phc_dr_advance": ([P(DrArgs), c_p], c_i32),
     "phc_clip_scratch_bytes": ([c_i64, c_i32], c_i64),
     "phc_clip_process": ([P(ClipArgs), c_p], c_i32),
+    "phc_clip_real_scratch_bytes": ([c_i64, c_i32, c_i32, c_i32], c_i64),
+    "phc_clip_process_real": ([P(ClipRealArgs), c_p], c_i32),
     "phc_teleop_rewards": ([P(MotionLib), P(TeleopArgs), c_p], c_i32),
     "phc_stream_track": ([P(Model), P(ImParams), P(StreamArgs), c_p], c_i32),
     "phc_dataset_record": ([P(RecordArgs), c_p], c_i32),

@@ -159,6 +159,24 @@ def clip_args_struct(num_clips, num_frames, num_bodies, num_trees, parents, loca
     return a
 
 
+CLIP_REAL_ARRAYS = ("parents", "offsets", "rest_mat", "pose_aa", "trans", "clip_start", "clip_dt", "contact_body", "contact_pos", "contact_radius")
+
+
+def clip_real_args_struct(num_clips, num_frames, num_bodies, num_ext, num_contacts, fix_height, scratch, scratch_bytes, frames, frame_stride=None, **arrays):
+    """phc_clip_real_args_t (phc_clip_process_real): `arrays` holds every name of CLIP_REAL_ARRAYS as a torch tensor / numpy array, a raw address (a view into one
+    staging buffer) or None."""
+    assert set(arrays) == set(CLIP_REAL_ARRAYS), sorted(set(arrays) ^ set(CLIP_REAL_ARRAYS))
+    a = L.ClipRealArgs()
+    a.num_clips, a.num_bodies, a.num_ext, a.num_contacts, a.num_frames = int(num_clips), int(num_bodies), int(num_ext), int(num_contacts), int(num_frames)
+    a.fix_height = 1 if fix_height else 0
+    a.frame_stride = frame_stride_for(int(num_bodies), int(num_ext), 1) if frame_stride is None else int(frame_stride)
+    addr = lambda x: x if x is None or isinstance(x, int) else ptr(x)
+    for k in CLIP_REAL_ARRAYS:
+        setattr(a, k, addr(arrays[k]))
+    a.scratch, a.frames, a.scratch_bytes = addr(scratch), addr(frames), int(scratch_bytes)
+    return a
+
+
 FIT_ARRAYS = ("parents", "offsets", "rest", "axis", "range", "match_body", "match_slot", "subtree", "clip_start", "clip_start_host", "target",
               "root_trans_offset", "dof", "dof_m", "dof_v", "root_rot", "root_rot_m", "root_rot_v", "root_off", "root_off_m", "root_off_v", "step", "loss")
 

@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #   domain randomisation: phc_sim_dr.hip holds the DR instantiations of the stepper's kernel and is compiled with phc_sim.hip's flags; phc_dr.hip (control delay,
 #     velocity push) like the push schedule -- its state and draws are bit-equal to the host build of phc_dr.h.
 #   clip processing (phc_clip.hip): fp64, no contraction, no fast-math -- it restates process_clip (motion_lib.py) operation by operation and is compared with it
-#     at one fp32 rounding.
+#     at one fp32 rounding.  phc_clip_real.hip (the robots' clips: matrix FK, height fix) the same, against process_clip_real.
 #   teleop rewards (phc_teleop.hip): like phc_dr.hip -- no contraction, no fast-math: its sums and its integer state follow the host build of phc_teleop.h.
 #   distillation (phc_distill.hip): like the learner kernels -- bandwidth-bound passes; IEEE division / exp and no contraction, so the SiLU follows its fp32 statement
 #     (phc_distill.h) operation by operation.
@@ -33,10 +33,10 @@ SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_
            "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_sim_plain.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
            "phc_push.hip": ["-ffp-contract=off"], "phc_sim_dr.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_dr.hip": ["-ffp-contract=off"],
-           "phc_clip.hip": ["-ffp-contract=off"], "phc_teleop.hip": ["-ffp-contract=off"],
+           "phc_clip.hip": ["-ffp-contract=off"], "phc_clip_real.hip": ["-ffp-contract=off"], "phc_teleop.hip": ["-ffp-contract=off"],
            "phc_stream.hip": ["-ffp-contract=off"], "phc_distill.hip": ["-ffp-contract=off"],
            "phc_fit.hip": ["-ffp-contract=off"], "phc_getup.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_getup.h", os.path.join("..", "..", "include", "phc_amd.h")]
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_getup.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

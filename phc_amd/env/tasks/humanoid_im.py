@@ -783,7 +783,7 @@ class HumanoidIm:
                                    "min_length": self._min_motion_len, "max_length": -1, "im_eval": flags.im_eval,
                                    "multi_thread": False, "smpl_type": self.humanoid_type, "randomrize_heading": True, "step_dt": self.dt,
                                    "heading_rng": self.cfg["env"].get("heading_rng", "persistent"),
-                                   "clip_processing": self.cfg["env"].get("clip_processing", "host"),   # `device`: load_motions' FK / velocities as HIP launches (SMPL family)
+                                   "clip_processing": self.cfg["env"].get("clip_processing", "host"),   # `device`: load_motions' FK / velocities as HIP launches (SMPL family and robots)
                                    "rank": int(self.cfg.get("rank", os.environ.get("RANK", 0)))})   # per-rank heading / crop stream (run_hydra.py:121 seeds per rank)
         if self._is_robot:  # humanoid_im.py:342-359
             motion_lib_cfg["robot"], motion_lib_cfg["robot_model"] = self.cfg["robot"], self.model

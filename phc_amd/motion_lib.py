@@ -19,7 +19,8 @@ What is different inside (MI355X-first):
     frames; the random heading is applied per env *after* the per-clip FK (rotation about z commutes
     with FK, np.gradient and the gaussian filter), so a clip shared by many envs is processed once;
     `clip_processing: device` runs the same per-clip arithmetic as two fp64 HIP launches instead
-    (`process_clips_device`, phc_amd/csrc/phc_clip.hip; SMPL family, opt-in).
+    (`process_clips_device`, phc_amd/csrc/phc_clip.hip; opt-in), and the robots' clips -- height fix, matrix FK, extended
+    bodies -- as three (`process_robot_clips_device`, phc_amd/csrc/phc_clip_real.hip; at least 3 frames per clip).
 """
 import os
 from enum import Enum
@@ -333,7 +334,8 @@ def _run_clip_chunk(args):
 # phc_clip_process (csrc/phc_clip.hip) is `process_clip` + the fp32 packing for concatenated clips of the SMPL family.  The host's part is the upload: the crops go
 # as fp64 through a pinned staging buffer (two slots, so that filling one overlaps the copy of the other) into one device input buffer; whole clips are grouped into
 # chunks of at most `chunk_frames` frames, which bounds staging, input and scratch (24 bodies, 262 144 frames: 208 MB per staging slot, 208 MB input, 303 MB scratch)
-# whatever the draw.  The buffers are kept per device and re-used by later calls.
+# whatever the draw.  The buffers are kept per device and re-used by later calls.  phc_clip_process_real (csrc/phc_clip_real.hip) is the robot branch of
+# `_run_clip_job` -- height fix, `process_clip_real`, packing -- behind the same staging (`process_robot_clips_device`).
 CLIP_PROCESSING = ("host", "device")
 _CLIP_STAGE = {}
 CLIP_TIMING = None   # scripts/clip_load_time.py puts a list here: per chunk the HIP events (upload begins, upload done, launches done)
@@ -488,6 +490,122 @@ def process_clips_device(parents, local_translations, clip_tree, quats, trans, f
     return frames
 
 
+def validate_robot_clip_inputs(consts, pose_aa_list, trans_list, fps_list):
+    """What phc_clip_process_real leaves to its caller, for the constants of `MotionLibReal._clip_consts`: -> dict of parents i32 [NB+E], offsets f64 [NB+E, 3],
+    rest_mat f64 [NB+E, 3, 3] (`_quat_xyzw_to_mat` of the rest rotations: both sides start from the same numbers), contact_body i32 [C], contact_pos f64
+    [C, 3], contact_radius f64 [C], fix_height, num_bodies, num_ext, frames per clip i64 [U], dt f64 [U]; ValueError otherwise."""
+    par = np.ascontiguousarray(np.concatenate([np.asarray(consts["parent"]).reshape(-1), np.asarray(consts["ext_parent"]).reshape(-1)]), dtype=np.int32)
+    nb, J = int(consts["num_bodies"]), par.shape[0]
+    ne = J - nb
+    if nb < 1 or ne < 0 or nb != np.asarray(consts["parent"]).reshape(-1).shape[0]:
+        raise ValueError(f"num_bodies {nb} does not match the {J - ne} parents of the model")
+    if J > abi.MAX_BODIES:
+        raise ValueError(f"clip processing on the device takes at most {abi.MAX_BODIES} bodies including the extended ones, not {nb} + {ne}")
+    off = np.ascontiguousarray(np.concatenate([np.asarray(consts["local_translation"], np.float64).reshape(-1, 3), np.asarray(consts["ext_pos"], np.float64).reshape(-1, 3)]))
+    rest = np.concatenate([np.asarray(consts["local_rotation"], np.float64).reshape(-1, 4), np.asarray(consts["ext_rot"], np.float64).reshape(-1, 4)])
+    if off.shape != (J, 3) or rest.shape != (J, 4):
+        raise ValueError(f"offsets {off.shape} / rest rotations {rest.shape} are not [{J}, 3] / [{J}, 4]")
+    if par[0] >= 0 or any(par[j] >= j for j in range(J)) or (par[1:nb] < 0).any() or (par[nb:] >= nb).any() or (par[nb:] < 0).any():
+        raise ValueError("body 0 must be the only root, every parent must precede its child and an extended body hangs off a simulated one")
+    fix = bool(consts["fix_height"])
+    cb = np.ascontiguousarray(np.asarray(consts["contact_body"]).reshape(-1), dtype=np.int32)
+    cp = np.ascontiguousarray(np.asarray(consts["contact_pos"], np.float64).reshape(-1, 3))
+    cr = np.ascontiguousarray(np.asarray(consts["contact_radius"], np.float64).reshape(-1))
+    if cp.shape[0] != cb.shape[0] or cr.shape[0] != cb.shape[0]:
+        raise ValueError(f"contact arrays disagree: {cb.shape} bodies, {cp.shape} positions, {cr.shape} radii")
+    if fix and (cb.shape[0] < 1 or cb.min() < 0 or cb.max() >= nb):
+        raise ValueError(f"the height fix needs at least one contact point, each on one of the {nb} simulated bodies")
+    U = len(pose_aa_list)
+    if U < 1 or len(trans_list) != U or len(fps_list) != U:
+        raise ValueError("one pose track, translation track and fps per clip (at least one clip)")
+    nf = np.zeros(U, dtype=np.int64)
+    for u, (p, t) in enumerate(zip(pose_aa_list, trans_list)):
+        if p.ndim != 3 or p.shape[2] != 3 or p.shape[1] < J or t.shape != (p.shape[0], 3):
+            raise ValueError(f"clip {u}: pose_aa {p.shape} / translations {t.shape} are not [T, >= {J}, 3] / [T, 3]")
+        if p.shape[0] < 3:
+            raise ValueError(f"clip {u} has {p.shape[0]} frame(s): a robot clip needs at least 3 (its last joint velocity is the second-to-last difference)")
+        nf[u] = p.shape[0]
+    f = np.asarray(fps_list, dtype=np.float64)
+    if not (np.isfinite(f).all() and (f > 0).all()):
+        raise ValueError("fps must be positive")
+    return dict(parents=par, offsets=off, rest_mat=np.ascontiguousarray(_quat_xyzw_to_mat(rest[:, [1, 2, 3, 0]])), contact_body=cb, contact_pos=cp, contact_radius=cr,
+                fix_height=fix, num_bodies=nb, num_ext=ne, nf=nf, dt=1.0 / f)
+
+
+def process_robot_clips_device(consts, pose_aa_list, trans_list, fps_list, device, chunk_frames=262144):
+    """The robot twin of `process_clips_device`: the device counterpart of the robot branch of `_run_clip_job` per clip + concatenation -- the packed fp32 frame
+    records [F, stride] of all clips as ONE device tensor, computed by phc_clip_process_real on torch's current stream.  consts: `MotionLibReal._clip_consts`;
+    pose_aa_list / trans_list: U arrays [T, >= NB+E, 3] / [T, 3]; fps_list: U numbers.  No CPU fallback: a device that is not a HIP device is an error."""
+    poses = [p.numpy() if isinstance(p, torch.Tensor) else np.asarray(p) for p in pose_aa_list]
+    trans = [t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in trans_list]
+    v = validate_robot_clip_inputs(consts, poses, trans, fps_list)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"clip_processing=device runs on the HIP device only (no CPU fallback), not on {device}; use clip_processing=host")
+    lib = L.load()
+    if not hasattr(lib, "phc_clip_process_real"):
+        raise RuntimeError("this build of libphc_amd.so has no phc_clip_process_real; use clip_processing=host")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    nb, ne, nf, dt = v["num_bodies"], v["num_ext"], v["nf"], v["dt"]
+    J, C_, F_ = nb + ne, v["contact_body"].shape[0], int(nf.sum())
+    stride = abi.frame_stride_for(nb, ne, 1)
+    stage = _CLIP_STAGE.setdefault(device, _ClipStage(device))
+    stage.uses += 1
+    first = np.concatenate([[0], np.cumsum(nf)])
+    chunks = _clip_chunks(nf, int(chunk_frames))
+    names = ("pose_aa", "trans", "offsets", "rest_mat", "contact_pos", "contact_radius", "clip_dt", "clip_start", "parents", "contact_body")
+
+    def layout(u0, u1):
+        # one buffer, the 8-byte types first: pose_aa [fc, J, 3] | trans [fc, 3] | offsets | rest_mat | contact_pos | contact_radius | clip_dt [n] f64 | clip_start
+        # [n + 1] i64 | parents [J] i32 | contact_body [C] i32
+        n, fc = u1 - u0, int(first[u1] - first[u0])
+        sizes = (fc * J * 24, fc * 24, J * 24, J * 72, C_ * 24, C_ * 8, n * 8, (n + 1) * 8, J * 4, C_ * 4)
+        return n, fc, sizes, [int(o) for o in np.concatenate([[0], np.cumsum([(s + 63) // 64 * 64 for s in sizes])])]
+
+    scratch_of = lambda u0, u1: int(lib.phc_clip_real_scratch_bytes(int(first[u1] - first[u0]), nb, ne, u1 - u0))
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream()
+        if stage.stream is not None and stage.stream != stream:
+            stage.stream.synchronize()   # (the buffers' last user ran on another stream)
+        stage.stream = stream
+        frames = torch.empty((F_, stride), dtype=torch.float32, device=device)
+        # sized once for the call's largest chunk: no buffer is replaced while an earlier chunk's launches may still read it
+        dev_in, scratch = stage.device_buffers(max(layout(*c)[3][-1] for c in chunks), max(scratch_of(*c) for c in chunks))
+        for u0, u1 in chunks:
+            n, fc, sizes, offs = layout(u0, u1)
+            k, host = stage.slot(offs[-1])
+            hv = host.numpy()
+            view = lambda i, dtype, shape: hv[offs[i]:offs[i] + sizes[i]].view(dtype).reshape(shape)
+            np.concatenate([p[:, :J] for p in poses[u0:u1]], axis=0, out=view(0, np.float64, (fc, J, 3)), casting="same_kind")
+            np.concatenate(trans[u0:u1], axis=0, out=view(1, np.float64, (fc, 3)), casting="same_kind")
+            view(2, np.float64, (J, 3))[...] = v["offsets"]
+            view(3, np.float64, (J, 3, 3))[...] = v["rest_mat"]
+            view(4, np.float64, (C_, 3))[...] = v["contact_pos"]
+            view(5, np.float64, (C_,))[...] = v["contact_radius"]
+            view(6, np.float64, (n,))[...] = dt[u0:u1]
+            view(7, np.int64, (n + 1,))[...] = first[u0:u1 + 1] - first[u0]
+            view(8, np.int32, (J,))[...] = v["parents"]
+            view(9, np.int32, (C_,))[...] = v["contact_body"]
+            timing = None if CLIP_TIMING is None else [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            if timing:
+                timing[0].record(stream)
+            dev_in[:offs[-1]].copy_(host[:offs[-1]], non_blocking=True)
+            if stage.events[k] is None:
+                stage.events[k] = torch.cuda.Event()
+            stage.events[k].record(stream)
+            if timing:
+                timing[1].record(stream)
+            base = dev_in.data_ptr()
+            args = abi.clip_real_args_struct(n, fc, nb, ne, C_, v["fix_height"], scratch, scratch_of(u0, u1), frames[int(first[u0]):int(first[u1])], stride,
+                                             **{name: base + offs[i] for i, name in enumerate(names)})
+            L.check(lib.phc_clip_process_real(args, stream.cuda_stream), "phc_clip_process_real")
+            if timing:
+                timing[2].record(stream)
+                CLIP_TIMING.append(timing)
+    return frames
+
+
 class MotionLibBase:
     """See module docstring.  Mirrors reference MotionLibBase (motion_lib_base.py:114-567)."""
 
@@ -587,9 +705,10 @@ class MotionLibBase:
         workers = int(self.m_cfg.get("num_workers", 0)) or default_pool_workers()
         uniq_frames = None
         if _clip_processing_of(self.m_cfg) == "device":
-            # `clip_processing: device` -- the same pairs through phc_clip_process: the records are born on the device, no worker pool is started
+            # `clip_processing: device` -- the same pairs through phc_clip_process / phc_clip_process_real: the records are born on the device, no worker
+            # pool is started; the fps is what the family's branch of `_run_clip_job` returns
             uniq_frames = self._process_clips_device(trees, jobs)
-            done = [(None, j[3], j[1].shape[0]) for j in jobs]
+            done = [(None, self._job_fps(j[3]), j[1].shape[0]) for j in jobs]
         elif len(jobs) >= int(self.m_cfg.get("pool_min_jobs", 256)) and workers > 1:
             # chunks of jobs, each carrying the (small) constants: no per-worker state to set up or to go stale between calls
             per = max(1, -(-len(jobs) // (workers * 8)))
@@ -668,6 +787,10 @@ class MotionLibBase:
             raise ValueError("clip_processing=device needs one topology for all skeleton trees")
         return process_clips_device(consts[0][0], np.stack([lt for _, lt in consts]), [j[0] for j in jobs], [j[1] for j in jobs], [j[2] for j in jobs],
                                     [j[3] for j in jobs], self._device, chunk_frames=int(self.m_cfg.get("clip_chunk_frames", 262144)))
+
+    def _job_fps(self, fps):
+        """The fps `_run_clip_job` returns for a job's fps (SMPL: as given)."""
+        return fps
 
     def _clip_payload(self, clip, tree_index, max_len, start):
         """One job of the clip workers: the crop of the clip's arrays (motion_lib_smpl.py:101-180 up to, not including, the per-env heading)."""
@@ -860,7 +983,12 @@ class MotionLibReal(MotionLibBase):
 
     def __init__(self, motion_lib_cfg):
         if _clip_processing_of(motion_lib_cfg) == "device":
-            raise NotImplementedError("clip_processing=device covers the SMPL family; the robots' matrix FK and extended bodies run with clip_processing=host")
+            # phc_clip_process_real is written for all-revolute articulations (one scalar joint coordinate per body below the root): said here, before any clip
+            # is loaded, rather than by a record of the wrong width at the first `load_motions`
+            m = motion_lib_cfg.get("robot_model", None)
+            if m is None or int(m.num_dof) != int(m.num_bodies) - 1:
+                raise NotImplementedError("clip_processing=device covers the SMPL family and all-revolute robot models (one DoF per body below the root); "
+                                          "this library has no such model: use clip_processing=host")
         self.robot_model = motion_lib_cfg["robot_model"]
         ext = list(motion_lib_cfg["robot"].get("extend_config", []))
         names = self.robot_model.body_names
@@ -919,6 +1047,14 @@ class MotionLibReal(MotionLibBase):
                 "local_rotation": np.asarray(m.local_rotation), "ext_parent": self.ext_parent, "ext_pos": self.ext_pos, "ext_rot": self.ext_rot,
                 "contact_body": np.asarray(m.contact_body), "contact_pos": np.asarray(m.contact_pos), "contact_radius": np.asarray(m.contact_radius),
                 "fix_height": self.fix_height != FixHeightMode.no_fix, "num_bodies": int(self.num_joints)}
+
+    def _process_clips_device(self, trees, jobs):
+        """Pass 2 on the device: the jobs' crops through `process_robot_clips_device` (height fix included) -> [sum of frames, stride] on the library's device."""
+        return process_robot_clips_device(self._clip_consts(trees), [j[1] for j in jobs], [j[2] for j in jobs], [j[3] for j in jobs], self._device,
+                                          chunk_frames=int(self.m_cfg.get("clip_chunk_frames", 262144)))
+
+    def _job_fps(self, fps):
+        return int(fps)   # fk_batch returns fps = int(1 / dt) (torch_humanoid_batch.py:219)
 
     def _clip_payload(self, clip, tree_index, max_len, start):
         trans = clip["root_trans_offset"]
