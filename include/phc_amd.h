@@ -764,6 +764,46 @@ int32_t phc_im_reset_from_state_masked(const phc_model_t* model, const phc_motio
  * offset_rand[i, 0..1] (each nullable), k[i] += 1 for EVERY env.  PHC_EINVAL: num_envs < 0, a null k, env_offset < 0 or env_offset + num_envs > 2^32. */
 int32_t phc_task_draws(int32_t num_envs, uint64_t key, int64_t env_offset, int32_t* k, float* cycle_phase /*[N]*/, float* offset_rand /*[N, 2]*/, void* stream);
 
+/* Observation noise and reference-sample dropout as one launch (csrc/phc_obs_aug.hip, per-lane code and the rules in full csrc/phc_obs_aug.h; additions to ABI 37,
+ * which stays 37): `+env.task_rng=device` with env.add_obs_noise / env.fut_tracks_dropout.  Same rules as HumanoidIm._fut_dropout + _add_obs_noise
+ * (humanoid_im.py:824-830, then :710-711), its own numbers.  For every SELECTED row i of obs [N, num_obs], with so = self_obs_size, T = num_samples,
+ * W = (num_obs - so) / T, P = (num_obs + 1) / 2:
+ *   dropout   T > 1 and dropout_p > 0: for each t < T with u(P + t, 0) < dropout_p, 0.0f into columns so + t W .. so + (t + 1) W - 1;
+ *   noise     noise_std > 0: every column c becomes obs[c] + noise_std * z[c] (the zeroed ones included), (z[2 j], z[2 j + 1]) the Box-Muller pair of the
+ *             uniforms a = u(j, 0), b = u(j, 1): r = sqrtf(-2 logf(1 - a)), theta = 2 pi b, r cosf(theta), r sinf(theta);
+ *   counter   k[i] += 1.
+ *   u(index, which) = hash_u01(splitmix64(key ^ (((k[i] << 16 | index) << 1 | which) * 0x9E6C63D0876A9A47)), env_offset + i).
+ * An unselected row is untouched and its counter stays.  Selection, exactly one form: all rows (row_flag and env_ids NULL); row_flag [N] int64, non-zero =
+ * selected; env_ids [n_ids] int64 in DEVICE memory, distinct ids in [0, N) (an id outside selects nothing; the same id twice is the caller's error).
+ * One workgroup per row, lanes along the columns; counters, dropout decisions and every stored 0.0f are bit-equal to the host build of phc_obs_aug.h, a noised
+ * element differs by the device's logf / sinf / cosf / sqrtf alone.
+ * PHC_EINVAL before any device work for: a null args / obs / k, num_envs / num_obs / num_samples / n_ids < 0, self_obs_size outside [0, num_obs], num_samples >= 1
+ * that does not divide num_obs - self_obs_size, both row_flag and env_ids, n_ids != 0 without env_ids, n_ids > num_envs, env_offset < 0 or env_offset + num_envs > 2^32, dropout_p
+ * outside [0, 1], noise_std < 0 (a NaN fails either).  PHC_EUNSUPPORTED: num_obs > 65536, num_samples > 1024.  num_envs == 0, or env_ids with n_ids == 0: 0 without a launch. */
+typedef struct {
+    int32_t num_envs, num_obs;                /* N, columns of a row */
+    int32_t self_obs_size, num_samples;       /* so, T */
+    float dropout_p, noise_std;
+    uint64_t key;                             /* stream key (the caller folds its seed into it) */
+    int64_t env_offset;                       /* global index of env 0 */
+    float* obs;                               /* [N, num_obs] contiguous */
+    int32_t* k;                               /* [N] calls that selected this env (the draw counter) */
+    const int64_t* row_flag;                  /* [N], nullable */
+    const int64_t* env_ids;                   /* [n_ids], nullable */
+    int64_t n_ids;
+} phc_obs_aug_args_t;
+int32_t phc_obs_augment(const phc_obs_aug_args_t* args /* host */, void* stream);
+
+/* The occlusion schedule of env.occl_training as one launch (csrc/phc_obs_aug.hip; rules: csrc/phc_obs_aug.h), the device form of
+ * HumanoidIm._update_occl_training (humanoid_im.py:1081-1092).  One lane per env i, for j = 0 .. J - 1, u = u(j, 0), v = u(j, 1) as above:
+ *   start = j != 0 && u < prob;  span = min(span_lo + floor(v * (span_hi - span_lo)), span_hi - 1);
+ *   count[i, j] = max((start ? span : count[i, j]) - 1, 0);  mask[i, j] = !(9 <= j && j < 24) (the reference overwrites the mask it derives from the counts:
+ *   the schedule never reaches the mask);  k[i] += 1 for EVERY env.  Bit-equal to the host build.
+ * PHC_EINVAL: a null k / count / mask, num_envs < 0, J < 0, env_offset < 0 or env_offset + num_envs > 2^32, prob outside [0, 1], span_hi <= span_lo.
+ * PHC_EUNSUPPORTED: J > 64.  num_envs == 0 returns 0 without a launch. */
+int32_t phc_occl_advance(int32_t num_envs, int32_t J, uint64_t key, int64_t env_offset, int32_t* k, float prob, int32_t span_lo, int32_t span_hi,
+                         int64_t* count /*[N, J]*/, uint8_t* mask /*[N, J]*/, void* stream);
+
 /* Domain randomisation in the stepper (csrc/phc_sim_dr.hip, the DR instantiations of the stepper's kernel; per-lane code csrc/phc_dr.h; additions to ABI 37, which
  * stays 37): phc_sim_step with PER-ENV physics.  With `dr` NULL, or both of its tensors NULL, and a model phc_sim_step accepts, the call IS phc_sim_step: same
  * checks, same launch, same bits.

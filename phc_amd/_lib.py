@@ -125,6 +125,11 @@ class GetupArgs(C.Structure):
                 ("fall_list", c_p), ("free_list", c_p)]
 
 
+class ObsAugArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_obs", c_i32), ("self_obs_size", c_i32), ("num_samples", c_i32), ("dropout_p", C.c_float), ("noise_std", C.c_float),
+                ("key", C.c_uint64), ("env_offset", c_i64), ("obs", c_p), ("k", c_p), ("row_flag", c_p), ("env_ids", c_p), ("n_ids", c_i64)]
+
+
 P = C.POINTER
 class SimDr(C.Structure):
     _fields_ = [("env_friction", c_p), ("torque_noise", c_p), ("k", c_p), ("key", C.c_uint64), ("env_offset", c_i64)]
@@ -267,6 +272,8 @@ _OPTIONAL_SIGNATURES = {
     "phc_refresh_body_state_masked": ([P(Model), P(SimState), c_p, c_p], c_i32),
     "phc_im_reset_from_state_masked": ([P(Model), P(MotionLib), P(ImParams), P(SimState), P(ImBuffers), c_p, c_p], c_i32),
     "phc_task_draws": ([c_i32, C.c_uint64, c_i64, c_p, c_p, c_p, c_p], c_i32),
+    "phc_obs_augment": ([P(ObsAugArgs), c_p], c_i32),
+    "phc_occl_advance": ([c_i32, c_i32, C.c_uint64, c_i64, c_p, C.c_float, c_i32, c_i32, c_p, c_p, c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

@@ -212,6 +212,23 @@ def getup_args_struct(num_envs, num_dof, key, env_offset=0, recovery_steps=0, **
     return a
 
 
+OBS_AUG_MAX_OBS, OBS_AUG_MAX_SAMPLES, OCCL_MAX_BODIES = 65536, 1024, 64   # csrc/phc_obs_aug.h: PHC_EUNSUPPORTED above
+
+
+def obs_aug_args_struct(obs, k, self_obs_size, num_samples, dropout_p, noise_std, key, env_offset=0, row_flag=None, env_ids=None, num_envs=None, num_obs=None, n_ids=None):
+    """phc_obs_aug_args_t (phc_obs_augment): `obs` [N, num_obs] fp32 contiguous and `k` [N] int32 as tensors / arrays (sizes taken from `obs`) or raw
+    addresses (then with `num_envs`, `num_obs`); one of `row_flag` [N] int64 / `env_ids` [n] int64 (n its length, or `n_ids` with an address), or neither = all rows."""
+    a = L.ObsAugArgs()
+    if num_envs is None:
+        num_envs, num_obs = obs.shape
+    a.num_envs, a.num_obs, a.self_obs_size, a.num_samples = int(num_envs), int(num_obs), int(self_obs_size), int(num_samples)
+    a.dropout_p, a.noise_std, a.key, a.env_offset = float(dropout_p), float(noise_std), int(key), int(env_offset)
+    for name, x in (("obs", obs), ("k", k), ("row_flag", row_flag), ("env_ids", env_ids)):
+        setattr(a, name, x if x is None or isinstance(x, int) else ptr(x))
+    a.n_ids = int(n_ids) if n_ids is not None else (0 if env_ids is None else int(env_ids.shape[0]))
+    return a
+
+
 def im_params_struct(dt, max_episode_length, reward_specs, power_reward, power_coefficient, enable_early_termination,
                      use_mean_termination, disable_collision_check, local_root_obs, root_height_obs, num_track_bodies,
                      track_slot, reset_mask, num_reset_bodies, first_reset_body, termination_distances, num_key_bodies, key_body_ids,

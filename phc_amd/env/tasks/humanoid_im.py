@@ -60,6 +60,8 @@ def _stream():
 
 TASK_DRAWS_TAG = 0x7461736B64726177   # ("taskdraw") stream tags of env.task_rng=device (perturb.stream_key)
 GETUP_DRAWS_TAG = 0x6765747570647277  # ("getupdrw")
+OBS_AUG_TAG = 0x6F62736E6F697365      # ("obsnoise") phc_obs_augment: observation noise + reference-sample dropout
+OCCL_TAG = 0x6F63636C75646572         # ("occluder") phc_occl_advance
 
 
 def launches_only(fn):
@@ -558,6 +560,14 @@ class HumanoidIm:
         if self._occl_training and (list(self._track_bodies) != list(self._body_names) or self._num_traj_samples > 1):
             raise NotImplementedError("occl_training: the reference indexes the mask by body id and by env row (humanoid_im.py:800,1181): "
                                       "full-body tracking, without fut_tracks")
+        # env.task_rng=device: the draw streams this task needs besides phc_task_draws' -- the attribute of the per-env counter -> the stream's tag.  Decided
+        # here, allocated in `_allocate_im_state`; empty in torch mode, which allocates nothing for them
+        self._aug_streams = {}
+        if self.task_rng == "device":
+            if self.add_obs_noise or self._fut_tracks_dropout:
+                self._aug_streams["_obs_aug_k"] = OBS_AUG_TAG
+            if self._occl_training:
+                self._aug_streams["_occl_k"] = OCCL_TAG
         # env.res_action (humanoid.py:327, humanoid_im.py:1094-1099): actions are residuals on the reference pose of the next frame
         self._res_action = bool(env.get("res_action", False))
 
@@ -598,6 +608,11 @@ class HumanoidIm:
             self._task_env_offset = int(self.cfg.get("rank", os.environ.get("RANK", 0))) * N
             self._task_draw_key = stream_key(self._task_seed, TASK_DRAWS_TAG)
             self._task_draw_k = torch.zeros(N, device=dev, dtype=torch.int32)
+        # ... and the streams of phc_obs_augment / phc_occl_advance, each with its own tag and counters, only where the option that draws from it is on
+        self._obs_aug_k = self._occl_k = None
+        for name, tag in self._aug_streams.items():
+            setattr(self, name, torch.zeros(N, device=dev, dtype=torch.int32))
+            setattr(self, name[:-1] + "key", stream_key(self._task_seed, tag))
         S, A = self._num_amp_obs_steps, self._num_amp_obs_per_step
         # AMP history (humanoid_amp.py:125-131): every env owns a strip of 2 S frames; the history is the window of S frames starting at
         # row `_amp_head` (newest first, like `_amp_obs_buf` of the reference).  A step writes its frame in the row BEFORE the window and
@@ -620,6 +635,8 @@ class HumanoidIm:
             self.random_occlu_idx = torch.zeros((N, J), dtype=torch.bool, device=dev)
             self.random_occlu_count = torch.zeros((N, J), **i64)
             self._occl_mask = torch.zeros((N, J), dtype=torch.uint8, device=dev)
+            if self._occl_k is not None:   # device draws: the launch writes count and mask in place; the attribute is a bool view of the mask
+                self.random_occlu_idx = self._occl_mask.view(torch.bool)
         if self._res_action:
             self._sim_struct.pd_ref = abi.ptr(self.ref_dof_pos)
         self.ref_motion_cache = {}
@@ -858,7 +875,12 @@ class HumanoidIm:
         if self.control_mode == "pd":
             self.actions = torch.clip(self.actions, -10, 10)   # humanoid.py:1568-1570
         if self._occl_training:   # humanoid_im.py:1112-1113
-            self._update_occl_training()
+            if self._occl_k is not None:   # env.task_rng=device: the same schedule as one launch (rules: csrc/phc_obs_aug.h)
+                L.check(self._lib.phc_occl_advance(self.num_envs, self._occl_mask.shape[1], self._occl_key, self._task_env_offset, self._occl_k.data_ptr(),
+                                                   self._occl_training_prob, 30, 60, self.random_occlu_count.data_ptr(), self._occl_mask.data_ptr(), _stream()),
+                        "phc_occl_advance")
+            else:
+                self._update_occl_training()
         if self._push is not None:   # (an env reset since the last step has progress 0: its push ends, a new pause is drawn)
             self._push.advance(self.progress_buf if self._push.capturable else self.progress_buf == 0)
         if self._dr is not None:     # control delay and velocity push (phc_dr_advance); `self.actions` stays the undelayed tensor
@@ -1044,10 +1066,22 @@ class HumanoidIm:
 
     def _task_rng_state(self):
         """The counters of the task's device draws as host tensors (HumanoidImGetup adds its own)."""
-        return {"draw_k": self._task_draw_k.cpu()}
+        state = {"draw_k": self._task_draw_k.cpu()}
+        if self._obs_aug_k is not None:
+            state["obs_k"] = self._obs_aug_k.cpu()
+        if self._occl_k is not None:
+            state.update(occl_k=self._occl_k.cpu(), occl_count=self.random_occlu_count.cpu())
+        return state
 
     def _load_task_rng_state(self, saved):
         self._task_draw_k.copy_(saved["draw_k"])
+        for key, dst in (("obs_k", self._obs_aug_k), ("occl_k", self._occl_k), ("occl_count", self.random_occlu_count if self._occl_k is not None else None)):
+            if dst is None:
+                continue
+            if key in saved and tuple(saved[key].shape) == tuple(dst.shape):
+                dst.copy_(saved[key])
+            else:
+                print(f"[phc_amd] task draw state `{key}` not restored: the checkpoint has none for this task; the draws start afresh", flush=True)
 
     def set_env_rng_state(self, state):
         self._reset_rng_dev.fill_(int(state.get("reset_rng_counter", 0)))
@@ -1073,13 +1107,14 @@ class HumanoidIm:
     def whole_step_capturable(self):
         """True when reset_done() + step() consist of launches and host bookkeeping only (no host-side random draws or syncs between them), so that
         the learner may capture them, with its own policy / critic segments, into ONE hipGraph per rollout step."""
-        # the draws of cycle_motion / far starts block a capture only while torch makes them (env.task_rng=torch): phc_task_draws is a launch.
+        # the draws of cycle_motion / far starts, of the occlusion schedule, the observation noise and the reference-sample dropout block a capture only while
+        # torch makes them (env.task_rng=torch): phc_task_draws, phc_occl_advance and phc_obs_augment are launches.
         # step / reset_done: the base class's, or an override known to be launches (and torch modules on device tensors) only -- marked `launches_only`:
         # MCPMixin.step is compose_actions (frozen torch modules under no_grad, no host read) plus the base step's three calls; HumanoidImGetup.reset_done in
         # device mode is four launches (`_reset_done_capturable`)
-        host_draws = (self.cycle_motion or self._far_start) and self.task_rng != "device"
-        return bool(self._reset_done_capturable() and not (host_draws or self._occl_training or self.add_obs_noise or self._fut_tracks_dropout
-                                                           or self.collect_dataset or self.obs_v == 5 or self._hist_obs_cols or flags.im_eval or flags.test)
+        host_draws = ((self.cycle_motion or self._far_start or self._occl_training or self.add_obs_noise or self._fut_tracks_dropout)
+                      and self.task_rng != "device")
+        return bool(self._reset_done_capturable() and not (host_draws or self.collect_dataset or self.obs_v == 5 or self._hist_obs_cols or flags.im_eval or flags.test)
                     and getattr(type(self).step, "launches_only", False)
                     and type(self).post_physics_step is HumanoidIm.post_physics_step and type(self).pre_physics_step is HumanoidIm.pre_physics_step)
 
@@ -1245,8 +1280,31 @@ class HumanoidIm:
 
     def _obs_noise(self, env_ids=None, reset_rows=False):
         self._one_hot_obs()
+        if self.task_rng == "device":
+            return self._obs_augment(env_ids, reset_rows)
         self._fut_dropout(env_ids, reset_rows)
         self._add_obs_noise(env_ids, reset_rows)
+
+    def _obs_augment(self, env_ids=None, reset_rows=False):
+        """env.task_rng=device: `_fut_dropout` + `_add_obs_noise` as ONE phc_obs_augment launch (rules: csrc/phc_obs_aug.h) -- dropout with probability 0.1
+        per reference sample, then N(0, 0.1) on every column, not in test mode.  Rows: all (the step), the id list (reset(env_ids)) or the rows whose reset
+        flag is set (reset_done: `reset_buf` as the launch's row flags, no host read)."""
+        if self._obs_aug_k is None or flags.test:
+            return
+        so, T = self.get_self_obs_size(), (self._num_traj_samples if self._fut_tracks_dropout else 1)
+        if (self.obs_buf.shape[1] - so) % T:
+            raise ValueError(f"fut_tracks_dropout: the task observation ({self.obs_buf.shape[1] - so} columns) does not divide into {T} reference samples")
+        form = None if env_ids is not None else bool(reset_rows)
+        hit = self.__dict__.setdefault("_obs_aug_args", {}).get(form)
+        ptrs = (self.obs_buf.data_ptr(), self.reset_buf.data_ptr(), so, T, self.add_obs_noise)
+        if hit is None or hit[1] != ptrs:
+            a = abi.obs_aug_args_struct(self.obs_buf, self._obs_aug_k, so, T, 0.1 if self._fut_tracks_dropout else 0.0, 0.1 if self.add_obs_noise else 0.0,
+                                        self._obs_aug_key, self._task_env_offset, row_flag=self.reset_buf if form else None)
+            hit = self._obs_aug_args[form] = (a, ptrs)
+        a = hit[0]
+        if env_ids is not None:
+            a.env_ids, a.n_ids = env_ids.data_ptr(), int(env_ids.shape[0])
+        L.check(self._lib.phc_obs_augment(a, _stream()), "phc_obs_augment")
 
     def _fut_dropout(self, env_ids=None, reset_rows=False):
         """env.fut_tracks_dropout (humanoid_im.py:824-830): every reference sample of a freshly computed task observation is zeroed with
