@@ -27,3 +27,15 @@ __device__ __forceinline__ int group_or(int v) {
 // The value that lane `src` (0 .. G-1) of the env's group holds, in every lane of the group.
 template <int G>
 __device__ __forceinline__ float group_bcast(float v, int src) { return __shfl(v, src, G); }
+
+// Hand-over through LDS between the lanes of ONE wavefront: what the lanes wrote (or added with ds_add) in front of this point is what any lane reads behind it.
+// PRECONDITION: the workgroup is a single wavefront (blockDim == 64).  The LDS operations of one wavefront are issued and performed in program order, so the
+// hardware needs nothing here -- a read issued right behind the write returns the written data -- and the AMDGPU memory model emits no instruction for a
+// wavefront-scope fence.  What is left is for the compiler: the two fences keep it from moving a memory access across the point, the wave barrier from moving
+// anything else of the schedule.  __syncthreads() in the same place is a workgroup-scope fence: an `s_waitcnt lgkmcnt(0)` that drains the LDS queue before the
+// next read may even be issued.  Kernels with larger workgroups keep __syncthreads().  (Not for hand-overs through global memory.)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "phc_aba.h"
+#include "phc_group.h"   // wave_sync
 #include "phc_sim_plain.h"
 #include "phc_dr.h"
 
@@ -117,7 +118,8 @@ __device__ __forceinline__ bool stage_aligned(const phc_sim_state_t& sim) {
 // ------------------------------------------------------------------------------------------
 // S10: the stepper.  One lane per body, GRP = 32 lanes per env (articulations of up to 32 bodies: two envs per wavefront) or
 // GRP = 64 (up to 64 bodies -- Unitree G1 has 38: one env per wavefront), blockDim = 64: ONE wavefront per workgroup, so
-// the level-synchronous tree sweeps synchronise with a single-wave barrier and every SIMD of the chip carries
+// the level-synchronous tree sweeps need no barrier instruction at all -- their hand-over points are wave_sync() (phc_group.h; a __syncthreads() there is not
+// "a 9-cycle s_barrier": the compiler drops the barrier of a one-wavefront workgroup and keeps the fence, an LDS-queue drain) -- and every SIMD of the chip carries
 // two independent dependency chains (2048 wavefronts at N = 4096).
 // Measured alternative (round 1, profiles/r01_notes.md): a level-major mapping (workgroup = 16 envs, wavefront = same
 // body of many envs, multi-wave barriers) runs ~100 % of its lanes but leaves 3 of 4 SIMDs idle at N = 4096 and needs
@@ -155,6 +157,27 @@ __device__ __forceinline__ bool stage_aligned(const phc_sim_state_t& sim) {
 #ifndef PHC_SIM_PLAIN_ITEMS
 #define PHC_SIM_PLAIN_ITEMS (ABA_PL_NO_CP_TAIL | ABA_PL_DRIVE_CONST | SIM_PL_LAG_PAIR)
 #endif
+// PHC_SIM_WAVE_ITEMS: the hand-over points of the kernel, in EVERY instantiation (profiles/stepper_wave_order/README.md); -DPHC_SIM_WAVE_ITEMS=0 builds the
+// library without the item (the A/B baseline of that README).
+//   SIM_WV_ORDER    every hand-over point of the kernel is wave_sync() (phc_group.h) instead of __syncthreads().  The workgroup is ONE wavefront (SIM_BLOCK), so
+//                   the compiler dropped the barrier instruction already; what __syncthreads() left was its workgroup-scope fence, an `s_waitcnt lgkmcnt(0)` that
+//                   drains the LDS queue at each of the ~119 points a wavefront passes per launch before the next level's read may be issued.  Everything that
+//                   crosses such a point goes from LDS to LDS within the wavefront (the list is in the README), and one wavefront's LDS operations are performed
+//                   in program order.
+// (Bits 2 and 8 were two more items of that README -- the lagged backward level-step's own products formed in front of the sweep, and the root's two level-steps
+//  as one; both were built, measured no faster, and are not in the source.)
+#define SIM_WV_ORDER 1
+#ifndef PHC_SIM_WAVE_ITEMS
+#define PHC_SIM_WAVE_ITEMS SIM_WV_ORDER
+#endif
+// threads per workgroup of every k_sim_step launch: one wavefront -- what wave_sync() (and the lane == body mapping) presupposes.  sim_launch_cm is the only
+// place that launches the kernel and launches it with this.
+constexpr int SIM_BLOCK = 64;
+static_assert(SIM_BLOCK == 64, "k_sim_step's hand-over points are wave_sync(): the workgroup must be one wavefront");
+template <int WV>
+__device__ __forceinline__ void sim_sync() {
+    if constexpr ((WV & SIM_WV_ORDER) != 0) wave_sync(); else __syncthreads();
+}
 template <bool PLAIN>
 __device__ __forceinline__ void pin_sim_plain(phc_sim_params_t& prm, phc_sim_state_t& sim, const float* __restrict__& actions, const int32_t* __restrict__& freeze,
                                               int& num_sim_calls) {
@@ -190,7 +213,7 @@ template <bool DR> struct DrArgs {};
 template <> struct DrArgs<true> { const float* env_friction; const float* torque_noise; const int32_t* k; uint64_t key; int64_t env_offset; };   // (phc_sim_dr_t)
 
 template <bool STEP, int JT, int GRP, bool SHAPES = false, bool RIGID = false, int OCC = 2, bool LAG = false, bool WRENCH = false, bool PLAIN = false, bool DR = false>
-__global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc_sim_params_t prm, phc_sim_state_t sim,
+__global__ __launch_bounds__(SIM_BLOCK, OCC) void k_sim_step(phc_model_t model_all, phc_sim_params_t prm, phc_sim_state_t sim,
                                                 const float* __restrict__ actions, const float* __restrict__ pd_off,
                                                 const float* __restrict__ pd_scale, const int32_t* __restrict__ freeze,
                                                 int num_sim_calls, const int64_t* __restrict__ env_ids, int num_listed, WrenchArgs<WRENCH> wr, DrArgs<DR> dr) {
@@ -208,6 +231,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     static_assert(!DR || (STEP && SHAPES && OCC == 2 && !WRENCH && !PLAIN), "the DR twins");
     static_assert(!PLAIN || (STEP && JT == PHC_JT_SPHERICAL && GRP == 32 && !SHAPES && !RIGID && OCC == 2 && LAG && !WRENCH), "the one plain instantiation");
     constexpr int PL = PLAIN ? (PHC_SIM_PLAIN_ITEMS) : 0;   // (phc_aba.h ABA_PL_*)
+    constexpr int WV = PHC_SIM_WAVE_ITEMS;
     pin_sim_plain<PLAIN>(prm, sim, actions, freeze, num_sim_calls);
     const int lane = threadIdx.x & (GRP - 1);
     const int grp = threadIdx.x / GRP;
@@ -265,12 +289,12 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
     if (!PHC_SKIP(8)) {
         const int jsteps = PLAIN ? SimPlainModel::jump_steps : model_jump_steps(model);
         aba_fk_jump_begin(L, body, x);
-        __syncthreads();
+        sim_sync<WV>();
         for (int k = 0; k < jsteps; ++k) {
             aba_fk_jump_step(L, k, x);
-            __syncthreads();
+            sim_sync<WV>();
             if (active) aba_write_kin(L, xslot(x, body), Xch::es, 6);
-            __syncthreads();
+            sim_sync<WV>();
         }
     }
     PHC_PROF(0)
@@ -291,9 +315,9 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
         if constexpr ((PL & ABA_PL_DRIVE_CONST) != 0) {
             if (active && L.level > 0) aba_plain_drive(L, pdrive, model_body(model, body), dt);
             if (active) { if (L.level == 0) L.diso = 0.f; aba_publish_diso(L, body, x); }
-            __syncthreads();
+            sim_sync<WV>();
             if (active) aba_fetch_diso(L, body, x);
-            __syncthreads();
+            sim_sync<WV>();
         }
         // (SIM_PL_LAG_PAIR: the two sub-steps of a simulate() call as one loop body, so that `lag` and the sub-step's parity are constants in each half)
 #pragma unroll SUBSTEP_UNROLL
@@ -314,9 +338,9 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             }
             if (prm.self_collision && !PHC_SKIP(0)) {   // body-body contact from the kinematics the last sweep left in the exchange slots
                 if (shape_lane) aba_publish_shape(L, lane, x, caps);   // body lanes: the primary capsules; the idle lanes behind them: the extra shapes
-                __syncthreads();
+                sim_sync<WV>();
                 if (env < sim.num_envs) aba_collide_pairs<PHC_SC_MAX_PER_LANE>(pair_all + threadIdx.x, 64, prm, dt, x, caps, near_pairs, s == 0);
-                __syncthreads();
+                sim_sync<WV>();
                 if (active) aba_collect_self(L, body, caps);
             }
             PHC_PROF(1)
@@ -360,16 +384,16 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             PHC_TL(4)
             if (JT == PHC_JT_SPHERICAL && rerooted && pass == 0 && !PHC_SKIP(2)) {   // reversed bodies take the drive terms of their solver parent's joint
                 if (active) aba_publish_drive(L, body, x, (PL & ABA_PL_DRIVE_CONST) != 0);
-                __syncthreads();
+                sim_sync<WV>();
                 if (active) aba_fetch_drive(L, body, x, (PL & ABA_PL_DRIVE_CONST) != 0);
-                __syncthreads();
+                sim_sync<WV>();
             }
             PHC_PROF(3)
             PHC_TL(5)
-            if (!PHC_SKIP(3)) for (int l = solver_depth; l >= 0; --l) { aba_backward_level<JT, (PL & ABA_PL_DRIVE_CONST) != 0>(L, l, body, x, lag); __syncthreads(); PHC_TL(120 + l) }
+            if (!PHC_SKIP(3)) for (int l = solver_depth; l >= 0; --l) { aba_backward_level<JT, (PL & ABA_PL_DRIVE_CONST) != 0>(L, l, body, x, lag); sim_sync<WV>(); PHC_TL(120 + l) }
             PHC_PROF(4)
             if (!PHC_SKIP(4)) {
-                for (int l = 0; l <= solver_depth; ++l) { aba_accel_level<JT>(L, l, body, x); __syncthreads(); PHC_TL(140 + l) }
+                for (int l = 0; l <= solver_depth; ++l) { aba_accel_level<JT>(L, l, body, x); sim_sync<WV>(); PHC_TL(140 + l) }
             }
             }
             if constexpr (DR) { if (RIGID && active && (s == nsub - 1 || prm.force_average)) { const phc_sim_params_t pf = dr_params(); aba_publish_contact_rigid(L, model, pf, sim, dt, env, body, true); } }
@@ -383,12 +407,12 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             PHC_PROF(6)
             PHC_TL(7)
             if (!PHC_SKIP(6)) aba_fk_jump_begin(L, body, x);   // kinematics by pointer jumping: jump_steps composition steps instead of max_level + 1 level-steps
-            __syncthreads();
+            sim_sync<WV>();
             for (int k = 0; k < (PHC_SKIP(6) ? 0 : jump_steps); ++k) {
                 aba_fk_jump_step(L, k, x);
-                __syncthreads();
+                sim_sync<WV>();
                 if (active) aba_write_kin(L, xslot(x, body), Xch::es, 6);
-                __syncthreads();
+                sim_sync<WV>();
                 PHC_TL(160 + k)
             }
             PHC_PROF(7)
@@ -406,7 +430,7 @@ __global__ __launch_bounds__(64, OCC) void k_sim_step(phc_model_t model_all, phc
             aba_store_state<JT>(L, st, nd, grp, body);
             aba_publish_body(L, st, nb, grp, body, true);
         }
-        __syncthreads();
+        sim_sync<WV>();
         stage_flush<E>(sim, xch_all, so, env0, nb, nd);
     } else if (active) {
         if (STEP) aba_store_state<JT>(L, sim, nd, env, body);
@@ -441,7 +465,7 @@ static void sim_launch_cm(const phc_model_t* model, const phc_sim_params_t& prm,
     constexpr bool LAG = STEP && !RIGID;
     const bool lag = LAG && prm.inertia_lag != 0;
     auto launch = [&](auto kernel, int64_t blocks) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, *model, prm, *sim, actions, off, scale, freeze, num_sim_calls, env_ids, num_listed, wr, dr);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(SIM_BLOCK), 0, stream, *model, prm, *sim, actions, off, scale, freeze, num_sim_calls, env_ids, num_listed, wr, dr);
     };
     if constexpr (!WRENCH && !DR && LAG && !SHAPES && JT == PHC_JT_SPHERICAL)   // (experiment knob, see OCC above)
         if (!wide && prm.lane_mapping == 3) return launch(k_sim_step<STEP, JT, 32, SHAPES, RIGID, 3>, (groups + 1) / 2);
