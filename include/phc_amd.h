@@ -1163,6 +1163,55 @@ typedef struct {
 int64_t phc_fit_scratch_bytes(int64_t num_frames, int32_t num_clips, int32_t num_bodies_ext);
 int32_t phc_fit_iterate(const phc_fit_args_t* args /* host; pointers device memory except clip_start_host */, int32_t iterations, void* stream);
 
+/* ---- Recording the simulated motion (csrc/phc_record.hip, per-lane code and the rules csrc/phc_record.h; an addition to ABI 37, which stays 37) ------------
+ * phc_motion_record: ONE launch per call, behind the post-physics launch on the same stream.  For every env i it appends one frame row to env i's block
+ * [cap, W] of the caller-owned `frames` [N, cap, W] (fp32) and one header row to `header` [N, cap, 4] (int32).  With NB simulated bodies, E extended
+ * (reference-only) ones and D DoFs a frame row is, in this order,
+ *   root_pos 3 | body_quat_global NB x 4 (rigid_body_state's rotations, xyzw, bit for bit: no hemisphere flip) | pose_aa (NB + E) x 3 |
+ *   dof_pos D | root linear and angular velocity 6 | reference time 1 | ref_body_pos NB x 3 (only with PHC_RECORD_REF)
+ * so W = phc_motion_record_width(NB, E, D, flags) = 3 + 4 NB + 3 (NB + E) + D + 7 (+ 3 NB).  pose_aa row 0 is quat_to_exp_map(root rotation) (phc_math.h), the
+ * row of a body on a spherical joint its three dof_pos values as they are (the DoF state already is the exp map), of a body on a revolute joint axis x dof_pos
+ * (axis from phc_model_t's body floats; shape block 0), of every other body -- the extended ones included -- zero.  The reference time is
+ * progress_buf dt + motion_start_times + motion_start_times_offset, the time post_physics_step looks up.  A header row is (segment id, progress_buf, motion id,
+ * the frame's flag).
+ * Per-env device state, all int32 [N]: len (frames held), seg (segment id), closed, dropped.  Row rule for env i with f = len[i]:
+ *   1. closed[i], or f >= min(cap, limit[i]) (limit nullable: cap): nothing is written; in the second case, unless closed[i], dropped[i] += 1;
+ *   2. otherwise the row is written at f and len[i] = f + 1;
+ *   3. then, if flag[i] != 0 (the caller passes terminate_buf in the sweep, reset_buf in play): closed[i] = 1 with PHC_RECORD_ONE_SEGMENT, else seg[i] += 1
+ *      (whether or not step 2 wrote the row, so that a segment cut short by `cap` still ends where the episode did).
+ * With PHC_RECORD_SEED steps 1 and 2 alone run and the stored flag is 0: the current state becomes a frame whatever `flag` holds (used right after a reset, so
+ * that frame 0 is the reset state).  Every decision is taken from device memory: no host read per call.
+ * PHC_EINVAL before any device access: a null model / args / model table / required pointer (ref_body_pos is required with PHC_RECORD_REF only, limit never),
+ * num_envs / num_bodies / num_dof / cap < 1, num_ext < 0, num_bodies / num_dof other than the model's, num_dof > 3 PHC_MAX_BODIES, a width other than phc_motion_record_width, dt not positive and finite, unknown flag bits;
+ * PHC_EUNSUPPORTED: num_bodies + num_ext > PHC_MAX_BODIES. */
+#define PHC_RECORD_REF 1
+#define PHC_RECORD_SEED 2
+#define PHC_RECORD_ONE_SEGMENT 4
+typedef struct {
+    int32_t num_envs, num_bodies, num_ext, num_dof;   /* N, NB, E, D */
+    int32_t cap, width;                       /* frames per env block; W */
+    int32_t flags;                            /* PHC_RECORD_* */
+    float   dt;
+    const float*   root_states;               /* [N, 13] */
+    const float*   dof_state;                 /* [N, D, 2] */
+    const float*   rigid_body_state;          /* [N, NB, 13] */
+    const int64_t* progress_buf;              /* [N] */
+    const int64_t* flag;                      /* [N] terminate_buf or reset_buf of this frame */
+    const int64_t* motion_ids;                /* [N] sampled motion ids */
+    const float*   motion_start_times;        /* [N] */
+    const float*   motion_start_times_offset; /* [N] */
+    const float*   ref_body_pos;              /* [N, NB, 3]; with PHC_RECORD_REF */
+    const int32_t* limit;                     /* [N] per-env frame limit; nullable */
+    float*   frames;                          /* [N, cap, W] out; 4-byte alignment suffices */
+    int32_t* header;                          /* [N, cap, 4] out */
+    int32_t* len;                             /* [N] state */
+    int32_t* seg;                             /* [N] state */
+    int32_t* closed;                          /* [N] state */
+    int32_t* dropped;                         /* [N] state */
+} phc_motion_record_args_t;
+int32_t phc_motion_record_width(int32_t num_bodies, int32_t num_ext, int32_t num_dof, int32_t flags);
+int32_t phc_motion_record(const phc_model_t* model /* host */, const phc_motion_record_args_t* args /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

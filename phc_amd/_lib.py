@@ -200,6 +200,16 @@ class RecordArgs(C.Structure):
                 ("reset", c_p)]
 
 
+RECORD_REF, RECORD_SEED, RECORD_ONE_SEGMENT = 1, 2, 4   # PHC_RECORD_*: phc_motion_record_args_t.flags
+
+
+class MotionRecordArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("num_ext", c_i32), ("num_dof", c_i32), ("cap", c_i32), ("width", c_i32), ("flags", c_i32),
+                ("dt", c_f), ("root_states", c_p), ("dof_state", c_p), ("rigid_body_state", c_p), ("progress_buf", c_p), ("flag", c_p), ("motion_ids", c_p),
+                ("motion_start_times", c_p), ("motion_start_times_offset", c_p), ("ref_body_pos", c_p), ("limit", c_p), ("frames", c_p), ("header", c_p),
+                ("len", c_p), ("seg", c_p), ("closed", c_p), ("dropped", c_p)]
+
+
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
@@ -274,6 +284,8 @@ _OPTIONAL_SIGNATURES = {
     "phc_task_draws": ([c_i32, C.c_uint64, c_i64, c_p, c_p, c_p, c_p], c_i32),
     "phc_obs_augment": ([P(ObsAugArgs), c_p], c_i32),
     "phc_occl_advance": ([c_i32, c_i32, C.c_uint64, c_i64, c_p, C.c_float, c_i32, c_i32, c_p, c_p, c_p], c_i32),
+    "phc_motion_record_width": ([c_i32, c_i32, c_i32, c_i32], c_i32),
+    "phc_motion_record": ([P(Model), P(MotionRecordArgs), c_p], c_i32),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_OPTIONAL_SIGNATURES)
 

@@ -401,3 +401,24 @@ def record_args_struct(num_envs, obs_dim, num_actions, step, capacity, **arrays)
             raise TypeError(f"phc_record_args_t has no field {name!r}")
         setattr(a, name, ptr(x))
     return a
+
+
+def motion_record_args_struct(num_envs, num_bodies, num_ext, num_dof, cap, dt, *, ref=False, seed=False, one_segment=False, **arrays):
+    """phc_motion_record_args_t (phc_motion_record): W follows from the sizes and `ref`; `arrays` are the pointer fields by name (torch tensors / numpy arrays,
+    contiguous)."""
+    a = L.MotionRecordArgs()
+    a.num_envs, a.num_bodies, a.num_ext, a.num_dof, a.cap = int(num_envs), int(num_bodies), int(num_ext), int(num_dof), int(cap)
+    a.flags = (L.RECORD_REF if ref else 0) | (L.RECORD_SEED if seed else 0) | (L.RECORD_ONE_SEGMENT if one_segment else 0)
+    a.width = motion_record_width(num_bodies, num_ext, num_dof, ref)
+    a.dt = float(np.float32(dt))
+    known = {n for n, _ in L.MotionRecordArgs._fields_}
+    for name, x in arrays.items():
+        if name not in known:
+            raise TypeError(f"phc_motion_record_args_t has no field {name!r}")
+        setattr(a, name, ptr(x))
+    return a
+
+
+def motion_record_width(num_bodies, num_ext, num_dof, ref=False):
+    """W of a frame row (phc_motion_record_width): root_pos 3 | body quaternions 4 NB | pose_aa 3 (NB + E) | dof_pos D | root velocities 6 | time 1 | ref_body_pos 3 NB."""
+    return 3 + 4 * int(num_bodies) + 3 * (int(num_bodies) + int(num_ext)) + int(num_dof) + 7 + (3 * int(num_bodies) if ref else 0)

@@ -1104,6 +1104,8 @@ class IMAmpAgent:
         `Humanoid.pth` every min(50, save_best_after) epochs; every `save_frequency` epochs (save_intermediate) also
         `Humanoid_{epoch:08d}.pth` and the evaluation sweep `eval()`, which re-weights the clip sampling (auto-PMCP, im_amp.py:126-132)
         and writes `failed_{epoch:010d}.pkl`."""
+        from ..motion_record import refuse_training
+        refuse_training(getattr(self.task, "cfg", None))   # `+record.motion` belongs to the player and the sweep
         push = getattr(self.task, "_push", None)
         if push is not None and not getattr(push, "capturable", False):
             # the captured rollout graph freezes the launch sequence and the state of the schedule's generator

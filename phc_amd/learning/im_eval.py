@@ -67,6 +67,25 @@ def metrics_from_sums(sums, count, num_bodies):
     return m
 
 
+class _Recorders:
+    """`collect_dataset` and `+record.motion` in one sweep: the batch hooks of both, in that order."""
+
+    def __init__(self, recs):
+        self.recs = recs
+
+    def begin_batch(self, num_steps, keys):
+        for r in self.recs:
+            r.begin_batch(num_steps, keys)
+
+    def record(self):
+        for r in self.recs:
+            r.record()
+
+    def end_batch(self):
+        for r in self.recs:
+            r.end_batch()
+
+
 def _begin_record(rec, lib, num_steps):
     """`collect_dataset`: the batch's reset has run; the recorder seeds its previous-observation buffer and lays out the batch block."""
     if rec is not None:
@@ -168,6 +187,12 @@ def evaluate(agent, output_dir=None, log=print):
     dist0 = getattr(agent, "dist", None)
     if getattr(task, "collect_dataset", False) and dist0 is not None and dist0.is_initialized() and dist0.get_world_size() > 1:
         raise ValueError(f"collect_dataset=True records in one process, not on {dist0.get_world_size()} ranks")
+    # `+record.motion=<out.pkl>` (phc_amd/motion_record.py): the simulated motion of every clip, one launch per env step behind the post-physics launch
+    from .. import motion_record
+    ropt = motion_record.options(getattr(task, "cfg", None))
+    if ropt is not None and dist0 is not None and dist0.is_initialized():
+        motion_record.refuse_ranks(dist0.get_world_size())
+    mrec = motion_record.MotionRecorder(task, ropt["max_frames"], ropt["ref"]) if ropt is not None else None
     agent.set_eval()
     lib_train = task._motion_lib
     saved = dict(td=task._termination_distances.clone(), test=flags.test, im_eval=flags.im_eval, start_idx=task.start_idx)
@@ -187,6 +212,10 @@ def evaluate(agent, output_dir=None, log=print):
         from .dataset_record import DatasetRecorder
         rec = DatasetRecorder(task)
     agent.last_dataset = None
+    agent.last_motion_record = None
+    drec = rec
+    if mrec is not None:
+        rec = mrec if drec is None else _Recorders([drec, mrec])
     push = getattr(task, "_push", None)                         # `+perturb.*` (phc_amd/perturb.py): the sweep then runs under scheduled pushes
     pushes0 = int(push.pushes) if push is not None else 0
     failed = np.zeros(U, dtype=np.float64)                      # 1 where the clip terminated before its last frame
@@ -247,6 +276,10 @@ def evaluate(agent, output_dir=None, log=print):
         lib_train.update_hard_sampling_weight(list(failed_keys))
     elif task.auto_pmcp_soft:
         lib_train.update_soft_sampling_weight(list(failed_keys))
+    if mrec is not None:   # the clip library of what the policy did, keyed like the source library
+        agent.last_motion_record = mrec
+        mrec.export(ropt["path"], log=log)
+    rec = drec
     if rec is not None:   # the player's dump (im_amp_players.py:200-214), after the last batch
         rms = getattr(agent, "running_mean_std", None)
         agent.last_dataset = rec

@@ -82,8 +82,16 @@ def main(argv=None):
 def play(agent, task, env, steps=300):
     """Deterministic-policy rollout (players.PpoPlayerContinuous with is_determenistic=True): mean reward and episode length."""
     agent.set_eval()
+    # `+record.motion=<out.pkl>` (phc_amd/motion_record.py): the rollout's motion as clips `<env>_<segment>`, split where reset_buf fired
+    from . import motion_record
+    ropt = motion_record.options(getattr(task, "cfg", None))
+    if ropt is not None:
+        motion_record.refuse_ranks(os.environ.get("WORLD_SIZE", "1"))
+    mrec = motion_record.MotionRecorder(task, ropt["max_frames"], ropt["ref"]) if ropt is not None else None
     pushes0 = int(task._push.pushes) if getattr(task, "_push", None) is not None else 0
     obs = env.reset()
+    if mrec is not None:
+        mrec.begin_play()
     rew_sum = torch.zeros(task.num_envs, device=task.device)
     ep_len = torch.zeros(task.num_envs, device=task.device)
     lens, rews = [], []
@@ -93,6 +101,8 @@ def play(agent, task, env, steps=300):
         for _ in range(steps):
             obs, r, done, info = env.step(agent.preprocess_actions(agent.get_action_values(obs)["mus"]))
             task.render()   # one frame per env step with `+render.video=DIR` (base_task.py:405-437); a no-op otherwise
+            if mrec is not None:   # (one launch behind the post-physics launch, before the finished envs are reset)
+                mrec.record()
             if streams:
                 stream_err += task.extras["stream_err"].mean()
             rew_sum += r
@@ -109,6 +119,10 @@ def play(agent, task, env, steps=300):
     out = {"episodes": int(lens.numel()), "mean_episode_length": float(lens.mean()), "mean_episode_reward": float(rews.mean()), "steps": steps}
     if getattr(task, "_push", None) is not None:   # `+perturb.*` (phc_amd/perturb.py): pushes started during the rollout, all envs
         out["perturb_pushes"] = int(task._push.pushes) - pushes0
+    if mrec is not None:
+        out.update(mrec.close())
+        mrec.export(ropt["path"], log=None)
+        agent.last_motion_record = mrec
     if streams:
         out["stream_err_mm"] = float(stream_err) / max(steps, 1) * 1000.0
     return out
