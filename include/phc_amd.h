@@ -625,6 +625,63 @@ typedef struct {
 int32_t phc_render(const phc_render_scene_t* scene /* host */, const phc_camera_t* cameras /* host, [views] */, int32_t views, int32_t width,
                    int32_t height, uint8_t* rgba, float* depth, int32_t* hit_id, void* stream);
 
+/* Renderer with triangle meshes (csrc/phc_render_mesh.hip; an addition to ABI 37, which stays 37): the scene of phc_render plus posed instances
+ * of triangle meshes (the robots' visual meshes), each traversed through a bounding-volume hierarchy.  The scene of a view is phc_render's, except:
+ *   * every instance i < num_instances is drawn.  Its mesh frame M_i in the world: rotation q = unit(q_body (x) quat_i) (xyzw, Hamilton product;
+ *     q_body = body_state[env, owner_i, 3:7] as stored), origin p_body + rotate(q_body, pos_i).  Vertices are never moved: a ray is taken into
+ *     the mesh frame.
+ *   * a capsule whose owner body owns at least one instance is neither drawn nor casts a shadow; bodies without an instance keep theirs.
+ *   * ground, markers, sky, light, shading formula, camera rays and the u8 rounding are phc_render's.
+ * Triangle hit: triangle (v0, v1, v2), e1 = v1 - v0, e2 = v2 - v0, g = e1 x e2.  It is two-sided; the point o + t d (t > 0) hits it when its
+ * barycentric coordinates u, v satisfy u >= 0, v >= 0, u + v <= 1.  A triangle with |g|^2 <= PHC_RENDER_MESH_MIN_CROSS^2 (m^4) or with d . g = 0
+ * is never hit.  Shading is flat: n = the unit of g, taken to the world, flipped so that n . d < 0; the base colour is the instance's rgb.  The
+ * shadow ray from (hit + 1e-3 n) is occluded by every drawn capsule, every marker and every instance (the hit triangle's own mesh included).
+ * Outputs: hit_id = PHC_RENDER_MESH_ID + i where instance i is hit first; tri_id i32 [V, H, W] (nullable) = tri_perm[k] of the hit triangle k,
+ * i.e. its index in the caller's original order, and -1 where no mesh is hit.
+ * Ties (deterministic, no atomics; "<" below is on the fp32 t the kernel computes): the first hit is the candidate of smallest t; among equal
+ * t a capsule or marker (lowest index) wins over an instance, the lowest instance index wins over a higher one, inside one instance the lowest
+ * position k in `triangles` wins, and any shape wins over the ground at equal t.
+ * Tree: nodes of one mesh are contiguous and in depth-first order: the first child of an interior node n is n + 1, and skip is the node that
+ * follows n's subtree (-1 after the last node of the mesh): traversal is node = (box hit and interior) ? node + 1 : skip, after testing a leaf's
+ * triangles.  skip must be > n or -1 (the kernel stops a traversal that would step backwards or leave [0, num_nodes)).  leaf < 0: interior; else
+ * leaf = 16 first + count: triangles first .. first + count - 1 (count <= 15) of `triangles`, leaves in increasing `first` along the depth-first
+ * order (the tie rule above relies on it).  A box may have zero thickness; a ray direction component may be 0 (then the slab holds the whole ray
+ * or none of it, by lo <= o <= hi).  Triangle and vertex indices outside their arrays are never dereferenced (such a triangle is skipped).
+ * meshes == NULL or num_instances == 0: rgba / depth / hit_id are phc_render's, byte for byte (the same kernel runs), tri_id is all -1.
+ * PHC_EINVAL before any device work for everything phc_render refuses, and for: num_instances outside [0, PHC_RENDER_MAX_INSTANCES];
+ * with num_instances > 0: a null instances / instances_dev / vertices / triangles / tri_perm / nodes, num_vertices < 1, num_triangles outside
+ * [1, PHC_RENDER_MAX_TRIANGLES], num_nodes outside [1, 2 PHC_RENDER_MAX_TRIANGLES], an instance owner outside [0, num_bodies), an instance root
+ * outside [0, num_nodes), nodes not 16-byte aligned; tri_id not 4-byte aligned. */
+#define PHC_RENDER_MESH_ID 2000
+#define PHC_RENDER_MAX_INSTANCES 128
+#define PHC_RENDER_MAX_TRIANGLES (1 << 22)
+#define PHC_RENDER_MESH_MIN_CROSS 1.0e-12f   /* m^2: |e1 x e2| at or below it = degenerate, never hit */
+typedef struct {
+    float lo[3];
+    int32_t skip;                     /* node after this subtree, -1 = end of the mesh */
+    float hi[3];
+    int32_t leaf;                     /* < 0 interior (first child = this + 1); else 16 * first triangle + count */
+} phc_bvh_node_t;                     /* 32 bytes, read as two 16-byte loads: the array must be 16-byte aligned */
+typedef struct {
+    int32_t owner;                    /* body that carries the instance */
+    int32_t root;                     /* root node of its mesh */
+    float pos[3], quat[4];            /* geom frame in the owner's body frame (xyzw) */
+    float center[3], radius;          /* bounding sphere of the mesh, mesh frame */
+    float rgb[3];                     /* base colour, linear 0..1 */
+} phc_mesh_instance_t;                /* 64 bytes */
+typedef struct {
+    int32_t num_vertices, num_triangles, num_nodes, num_instances;   /* NV, NT, NN, I */
+    const float* vertices;            /* device [NV, 3], mesh frames */
+    const int32_t* triangles;         /* device [NT, 3] vertex indices, in leaf order */
+    const int32_t* tri_perm;          /* device [NT]: index of triangle k in the caller's original order */
+    const phc_bvh_node_t* nodes;      /* device [NN] */
+    const phc_mesh_instance_t* instances;       /* HOST [I]: read by the argument checks */
+    const phc_mesh_instance_t* instances_dev;   /* device copy of the same [I]: read by the kernel */
+} phc_render_meshes_t;
+int32_t phc_render_mesh(const phc_render_scene_t* scene /* host */, const phc_render_meshes_t* meshes /* host; nullable */,
+                        const phc_camera_t* cameras /* host, [views] */, int32_t views, int32_t width, int32_t height, uint8_t* rgba, float* depth,
+                        int32_t* hit_id, int32_t* tri_id /* nullable */, void* stream);
+
 /* Evaluation sweep: tracking metrics accumulated on the device (csrc/phc_eval.hip; an addition to ABI 37, which stays 37).  One launch per env
  * step of a sweep batch replaces the host path's second reference lookup, its two [N, NB, 3] device-to-host copies and the numpy metric pass of
  * learning/im_eval.py (compute_metrics_per_clip).  One lane per body, 32-lane groups up to 32 bodies (64 above), 256-thread blocks.  Per env i:

@@ -105,6 +105,25 @@ class RenderScene(C.Structure):
                 ("sky_color", c_f * 3), ("light_dir", c_f * 3), ("ambient", c_f), ("diffuse", c_f)]
 
 
+RENDER_MESH_ID = 2000            # PHC_RENDER_MESH_ID
+RENDER_MAX_INSTANCES = 128       # PHC_RENDER_MAX_INSTANCES
+RENDER_MAX_TRIANGLES = 1 << 22   # PHC_RENDER_MAX_TRIANGLES
+RENDER_MESH_MIN_CROSS = 1.0e-12  # PHC_RENDER_MESH_MIN_CROSS
+
+
+class BvhNode(C.Structure):
+    _fields_ = [("lo", c_f * 3), ("skip", c_i32), ("hi", c_f * 3), ("leaf", c_i32)]
+
+
+class MeshInstance(C.Structure):
+    _fields_ = [("owner", c_i32), ("root", c_i32), ("pos", c_f * 3), ("quat", c_f * 4), ("center", c_f * 3), ("radius", c_f), ("rgb", c_f * 3)]
+
+
+class RenderMeshes(C.Structure):
+    _fields_ = [("num_vertices", c_i32), ("num_triangles", c_i32), ("num_nodes", c_i32), ("num_instances", c_i32), ("vertices", c_p),
+                ("triangles", c_p), ("tri_perm", c_p), ("nodes", c_p), ("instances", C.POINTER(MeshInstance)), ("instances_dev", c_p)]
+
+
 class EvalArgs(C.Structure):
     _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("root_idx", c_i32), ("step", c_i32), ("bound", c_i32), ("dt", c_f),
                 ("rigid_body_state", c_p), ("progress_buf", c_p), ("terminate_buf", c_p), ("motion_ids", c_p), ("motion_start_times", c_p),
@@ -252,6 +271,7 @@ _SIGNATURES = {
     "phc_ppo_loss_workspace": ([], c_i64),
     "phc_ppo_loss": ([c_p, c_p, c_i32] + [c_p] * 9 + [c_i64, c_i32, P(PpoParams), c_p, c_p, c_p, c_p, c_p], c_i32),
     "phc_render": ([P(RenderScene), P(Camera), c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p], c_i32),
+    "phc_render_mesh": ([P(RenderScene), P(RenderMeshes), P(Camera), c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p], c_i32),
     "phc_eval_accumulate": ([P(MotionLib), P(EvalArgs), c_p], c_i32),
     "phc_push_advance": ([P(PushArgs), c_p], c_i32),
 }

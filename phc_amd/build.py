@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #     same kernel (phc_sim_kernel.h) and is compiled with the same flags; so is phc_sim_plain.hip, the plain instantiation of the default SMPL task's launch (phc_sim_plain.h).
 #   learner kernels: bandwidth-bound passes; IEEE division / no contraction so the normalised values equal torch's.
 #   matrix-core kernels (phc_gemm.hip): no contraction either (the fp32 slab and bias sums are plain adds in a fixed order).
-#   renderer (phc_render.hip, off the training path): IEEE fp32 (no fast-math): its error bound assumes correctly rounded sqrt / division.
+#   renderer (phc_render.hip, phc_render_mesh.hip; off the training path): IEEE fp32 (no fast-math): its error bound assumes correctly rounded sqrt / division.
 #   evaluation metrics (phc_eval.hip): no contraction -- its reference positions are bit-equal to phc_motion_state's.
 #   push schedule (phc_push.hip): no contraction, no fast-math -- its integer state is bit-equal to the host build of phc_push.h.
 #   domain randomisation: phc_sim_dr.hip holds the DR instantiations of the stepper's kernel and is compiled with phc_sim.hip's flags; phc_dr.hip (control delay,
@@ -35,13 +35,13 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #     build of phc_record.h; the root's exp map and the robots' axis x angle rows differ by the device's elementary functions alone.
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_kernels_plain.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_sim_plain.hip": ["-ffast-math", "-fno-slp-vectorize"],
-           "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
+           "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_render_mesh.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
            "phc_push.hip": ["-ffp-contract=off"], "phc_sim_dr.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_dr.hip": ["-ffp-contract=off"],
            "phc_clip.hip": ["-ffp-contract=off"], "phc_clip_real.hip": ["-ffp-contract=off"], "phc_teleop.hip": ["-ffp-contract=off"],
            "phc_stream.hip": ["-ffp-contract=off"], "phc_distill.hip": ["-ffp-contract=off"],
            "phc_fit.hip": ["-ffp-contract=off"], "phc_getup.hip": ["-ffp-contract=off"],
            "phc_obs_aug.hip": ["-ffp-contract=off"], "phc_record.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", os.path.join("..", "..", "include", "phc_amd.h")]
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

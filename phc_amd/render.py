@@ -2,7 +2,7 @@
 
 Replaces the reference player's camera sensor and video writer (phc/env/tasks/base_task.py:176-195,405-437): the frames come from a kernel of
 our own because the GPU hosts have no display and no rasteriser.  What is drawn: every collision capsule of the env's articulation (boxes
-appear as their capsule stand-ins; the H1 / G1 visual meshes are not drawn), the ground z = 0 with a 1 m checker, the shadows of one
+appear as their capsule stand-ins; the H1 / G1 visual meshes are drawn only with `+render.meshes=<the robot's MJCF>`: render_mesh.py), the ground z = 0 with a 1 m checker, the shadows of one
 directional light and, optionally, the reference bodies of the next frame as 5 cm spheres (humanoid_im.py:597-619 `_update_marker`).
 
     python -m phc_amd.run test=True ... +render.video=out [+render.envs=4 +render.width=640 +render.height=480 +render.markers=True +render.follow=True]
@@ -119,14 +119,18 @@ def task_capsules(task):
     return torch.from_numpy(capsule_table(task.shape_models)).to(task.device)
 
 
-def render_envs(task, env_ids, cameras, width, height, markers=True, depth=False, hit_id=False, capsules=None):
+def render_envs(task, env_ids, cameras, width, height, markers=True, depth=False, hit_id=False, capsules=None, meshes=None):
     """Render envs `env_ids` of a HumanoidIm task (its rigid_body_state; markers = the task's ref_body_pos, the next frame's reference
     bodies) on the task's stream.  Reads simulator state only: no RNG draw, no task buffer written.  capsules: task_capsules(task), to
-    skip the upload."""
+    skip the upload.  meshes: an uploaded render_mesh.MeshSet, drawn through phc_render_mesh in place of the capsules of its bodies."""
     caps = task_capsules(task) if capsules is None else capsules   # (held until the launch: the scene keeps raw pointers only)
     env_shape = task._env_shape if len(task.shape_models) > 1 else None
     scene = scene_struct(caps, task.num_envs, task.num_bodies, task._rigid_body_state_reshaped, env_shape=env_shape,
                          markers=task.ref_body_pos if markers else None)
+    if meshes is not None:
+        from . import render_mesh
+        return render_mesh.render(scene, meshes, cameras, [int(e) for e in env_ids], width, height, depth=depth, hit_id=hit_id, device=task.device,
+                                  lib=task._lib)
     return render(scene, cameras, [int(e) for e in env_ids], width, height, depth=depth, hit_id=hit_id, device=task.device, lib=task._lib)
 
 
@@ -200,7 +204,9 @@ class TaskRecorder:
       render.envs    k: a grid of envs 0 .. k-1, one camera each (default 1: env 0, as the reference records)
       render.width / render.height   one view's size (default 640 x 480)
       render.markers draw the next frame's reference bodies (default flags.show_traj, as the reference)
-      render.follow  cameras follow their env's root (default True; False: the first placement stays)"""
+      render.follow  cameras follow their env's root (default True; False: the first placement stays)
+      render.meshes  path of the robot's MJCF: its visual meshes are drawn (phc_render_mesh) in place of the capsules of the bodies that carry one
+      render.mesh_color  asset (default: the MJCF rgba of each geom) or palette (the body palette)"""
 
     def __init__(self, task, rc):
         from .utils.flags import flags
@@ -212,6 +218,10 @@ class TaskRecorder:
         self.cameras = [Camera() for _ in range(self.k)]
         self._placed = False
         self.capsules = task_capsules(task)
+        self.meshes = None
+        if rc.get("meshes", None):
+            from .render_mesh import task_mesh_set
+            self.meshes = task_mesh_set(task, str(rc["meshes"]), str(rc.get("mesh_color", "asset")))
         rank = int(os.environ.get("RANK", "0"))        # (torchrun: every rank records its own envs into a directory of its own)
         self.recorder = VideoRecorder(os.path.join(str(rc["video"]), f"rank{rank}") if rank else str(rc["video"]), fps=max(1, int(round(1.0 / task.dt))), name=str(task.cfg.get("exp_name", "video")))
 
@@ -222,7 +232,7 @@ class TaskRecorder:
             for cam, r in zip(self.cameras, roots):
                 cam.follow(r)
             self._placed = True
-        frames = render_envs(t, range(self.k), self.cameras, self.width, self.height, markers=self.markers, capsules=self.capsules)
+        frames = render_envs(t, range(self.k), self.cameras, self.width, self.height, markers=self.markers, capsules=self.capsules, meshes=self.meshes)
         self.recorder.add(tile(frames, math.ceil(math.sqrt(self.k))))
 
     def close(self):
