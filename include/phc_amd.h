@@ -579,7 +579,8 @@ int32_t phc_ppo_loss(const void* mu, const void* value, int32_t is_bf16, const f
  *   * every collision capsule s < num_capsules of the env's shape block (a box is drawn as its capsule stand-in), posed by the owner body's
  *     rigid_body_state row (pos3, xyzw quaternion);
  *   * the ground plane z = 0 with a 1 m two-tone checker: ground_color[(floor(x) + floor(y)) & 1];
- *   * optional marker spheres (radius marker_radius) at markers[env, m];
+ *   * optional marker spheres at markers[env, m]: radius marker_radii[m] and colour marker_colors[m] where those arrays are given, else marker_radius
+ *     and marker_color for all (both NULL: the frames of a scene without the two fields, byte for byte); a marker of radius <= 0 is not drawn;
  *   * sky_color where a ray hits nothing.
  * Shading of a hit with unit normal n, base colour C (palette[owner % PHC_RENDER_PALETTE] for a capsule, marker_color, the checker tone):
  *   lit = max(n . light_dir, 0), set to 0 when the shadow ray from (hit + 1e-3 n) toward light_dir enters any capsule or marker at t > 0
@@ -621,6 +622,8 @@ typedef struct {
     float sky_color[3];
     float light_dir[3];               /* unit vector toward the light */
     float ambient, diffuse;
+    const float* marker_radii;        /* [M] radius of each marker; nullable = marker_radius for all */
+    const float* marker_colors;       /* [M, 3] colour of each marker, linear 0..1; nullable = marker_color for all */
 } phc_render_scene_t;
 int32_t phc_render(const phc_render_scene_t* scene /* host */, const phc_camera_t* cameras /* host, [views] */, int32_t views, int32_t width,
                    int32_t height, uint8_t* rgba, float* depth, int32_t* hit_id, void* stream);
@@ -764,6 +767,93 @@ typedef struct {
     float* force;                             /* [N, NB, 3] */
 } phc_push_args_t;
 int32_t phc_push_advance(const phc_push_args_t* args /* host */, void* stream);
+
+/* Thrown projectiles (csrc/phc_proj.hip, per-lane code and the rules line by line csrc/phc_proj.h; an addition to ABI 37, which stays 37): config group
+ * `projectile` (phc_amd/projectile.py).  One launch is one env step of `count` spheres per env, in front of the stepper: flight, ground bounce, collision test
+ * against every collision capsule of the model, and the impulse of a hit as a force and a torque on the struck body, which phc_sim_step_wrench holds over the
+ * env step.  A projectile is a point mass of radius `radius` without spin; its contact with the bodies is frictionless; projectiles do not touch each other.
+ * State per slot p < count and env i, arrays [P, N] (pos, vel: [P, N, 3]): life (env steps left, 0 = parked at z = -1000), countdown, thrown, hits, last_hit
+ * (the shape struck in this env step, -1 none), pos, vel, mass; k[i] is the env's launch count.  One lane group of 32 (num_shapes <= 32) or 64 lanes per env,
+ * lane s owns shape s and row s of force[i] / torque[i]; the winner of a sub-interval is a group-wide arg-min over (gap, shape index).  Per slot:
+ *   u[0..7] = proj_draws(key, env_offset + i, k, p): pause, body, mass, speed, distance, azimuth, elevation, spare -- counter-based hashes;
+ *   reset   = k == 0 or progress_buf[i] == 0: life = 0, countdown = pause = pause_lo + min(floor(u[0] (pause_hi - pause_lo + 1)), pause_hi - pause_lo), parked;
+ *   parked with countdown > 0: countdown -= 1.  Parked with countdown <= 0: a throw at body bodies[min(floor(u[1] num_listed), num_listed - 1)]:
+ *             m, speed s, distance d, elevation el uniform in their ranges, azimuth az = 2 pi u[5]; x_t, v_t the body's centre of mass and its velocity
+ *             (origin velocity + w x R com); t_f = d / s; x0 = x_t + d (cos el cos az, cos el sin az, sin el) with x0.z >= radius + 0.01;
+ *             v0 = (x_t + v_t t_f - x0) / t_f - 0.5 g t_f; life = life_steps, thrown += 1; flight starts in this launch;
+ *   flight (life > 0): `substeps` sub-intervals h = dt / substeps, each: v += g h; x += v h; then the ground: where x.z < radius and v.z < 0 the tangential
+ *             velocity shrinks by min(friction (1 + e) |v.z|, |v_t|), v.z = -e v.z, x.z = radius; then the bodies, unless the slot has struck in this launch:
+ *             every capsule (radius r_c > 0) is posed at the start of the step from its owner's row of rigid_body_state, its endpoints moved at first order
+ *             to the end of the sub-interval (t = (i + 1) h, endpoint velocity v_b + w x (a - x_b)); c = closest point of the segment, n = (x - c) / |x - c|
+ *             (z^ where they coincide), gap = |x - c| - radius - r_c, vn = (v - v_c) . n with v_c the endpoint velocities interpolated at c; candidates have
+ *             gap < 0 and vn < 0; the least gap wins, a tie goes to the lowest shape index; with r from the owner's centre of mass (moved to t at first order) to
+ *             the contact point c + r_c n and I_w^-1 = R I_b^-1 R^T:  j = -(1 + e) vn / (1/m + 1/m_b + n . ((I_w^-1 (r x n)) x r)),  v += j n / m,
+ *             force[i, owner] += -j n / dt, torque[i, owner] += r x (-j n / dt), hits += 1, last_hit = shape;
+ *   end of the launch: life -= 1, at 0 the slot parks and countdown = pause.  k[i] += 1.
+ * force / torque [N, NB, 3] hold exactly what acts in this env step: every row of every env is written once per launch, zero where nothing struck; two slots
+ * that strike one body add, in slot order.  No atomics, no two lanes store to one address: the launch is deterministic.  Integer state and floats equal the host
+ * build of phc_proj.h up to the sinf / cosf of the throw.
+ * PHC_EINVAL before any device work for: a null args or a null pointer in it other than progress_buf; num_envs < 0; num_bodies outside [1, PHC_MAX_BODIES];
+ * num_shapes outside [num_bodies, PHC_PROJ_MAX_SHAPES]; num_listed outside [1, PHC_MAX_BODIES]; count outside [1, PHC_PROJ_MAX_SLOTS]; pause_lo < 0, pause_hi <
+ * pause_lo or > 2^24; life_steps outside [1, 2^24]; substeps outside [1, 64]; dt or radius not positive and finite; gravity_z positive or not finite; restitution
+ * outside [0, 1]; friction negative or not finite; a mass, speed or distance range that is not 0 < lo <= hi < inf; an elevation range outside
+ * -pi/2 <= lo <= hi <= pi/2; env_offset < 0 or env_offset + num_envs > 2^32.  `bodies` and `owner` are device memory: the caller guarantees entries in
+ * [0, num_bodies) (phc_amd/projectile.py checks them before the upload).  num_envs == 0 returns 0 without a launch. */
+#define PHC_PROJ_MAX_SLOTS 4
+#define PHC_PROJ_MAX_SHAPES 64
+typedef struct {
+    int32_t num_envs, num_bodies, num_shapes; /* N, NB, collision shapes (primary capsules first, then the extra ones) */
+    int32_t num_listed;                       /* entries of `bodies` */
+    int32_t count;                            /* P: projectile slots per env */
+    int32_t pause_lo, pause_hi;               /* env steps between parking and the next throw */
+    int32_t life_steps;                       /* env steps a thrown projectile lives */
+    int32_t substeps;                         /* sub-intervals of the env step */
+    float dt, gravity_z;                      /* env step (s); gravity along z (<= 0) */
+    float radius, restitution, friction;      /* sphere radius (m); restitution e of ground and bodies; the plane's friction */
+    float mass_lo, mass_hi, speed_lo, speed_hi, dist_lo, dist_hi, elev_lo, elev_hi;   /* kg, m/s, m, radians */
+    uint64_t key;                             /* stream key */
+    int64_t env_offset;                       /* global index of env 0 */
+    const int32_t* bodies;                    /* device [num_listed] target bodies */
+    const float* capsules;                    /* [num_shapes, 7] a3, b3 in the owner's frame, radius (<= 0: no shape) */
+    const int32_t* owner;                     /* [num_shapes] */
+    const float* body_com;                    /* [NB, 3] centre of mass, body frame */
+    const float* body_inv_mass;               /* [NB] */
+    const float* body_inv_inertia;            /* [NB, 9] inverse inertia about the centre of mass, body frame, row-major */
+    const float* rigid_body_state;            /* [N, NB, 13] */
+    const int64_t* progress_buf;              /* [N]; nullable = no env was reset */
+    int32_t* life;                            /* [P, N] */
+    int32_t* countdown;                       /* [P, N] */
+    int32_t* thrown;                          /* [P, N] */
+    int32_t* hits;                            /* [P, N] */
+    int32_t* last_hit;                        /* [P, N] */
+    int32_t* k;                               /* [N] */
+    float* pos;                               /* [P, N, 3] */
+    float* vel;                               /* [P, N, 3] */
+    float* mass;                              /* [P, N] */
+    float* force;                             /* [N, NB, 3] */
+    float* torque;                            /* [N, NB, 3] */
+} phc_proj_args_t;
+int32_t phc_proj_advance(const phc_proj_args_t* args /* host */, void* stream);
+
+/* The two row copies that keep a task with projectiles bit-equal to the same task without them wherever nothing struck (csrc/phc_proj.hip).  The task steps
+ * its simulator tensors through the launch it would take without the group (phc_sim_step), steps a shadow copy of them through phc_sim_step_wrench with the
+ * wrench of phc_proj_advance, and takes the shadow's rows for the struck envs only.  One launch each, one 256-thread block per env, over num_sets tensor
+ * pairs of `width[s]` floats per env:
+ *   PHC_PROJ_SNAPSHOT  shadow[s][env] = base[s][env] for every env (before the two stepper launches);
+ *   PHC_PROJ_SELECT    base[s][env] = shadow[s][env] for every env with last_hit[p, env] >= 0 in any slot p < count; no other element is written.
+ * PHC_EINVAL before any device work: a null args, num_envs < 0, num_sets outside [1, PHC_PROJ_MAX_ROWSETS], a mode other than the two, a null base / shadow
+ * pointer or a width < 1 in a used set, and with PHC_PROJ_SELECT a null last_hit or count outside [1, PHC_PROJ_MAX_SLOTS].  num_envs == 0: no launch. */
+#define PHC_PROJ_MAX_ROWSETS 8
+#define PHC_PROJ_SNAPSHOT 0
+#define PHC_PROJ_SELECT 1
+typedef struct {
+    int32_t num_envs, count, num_sets, mode;
+    const int32_t* last_hit;                  /* [P, N] of phc_proj_args_t; read by PHC_PROJ_SELECT only */
+    float* base[PHC_PROJ_MAX_ROWSETS];        /* [N, width[s]] */
+    float* shadow[PHC_PROJ_MAX_ROWSETS];      /* [N, width[s]] */
+    int32_t width[PHC_PROJ_MAX_ROWSETS];
+} phc_proj_rows_t;
+int32_t phc_proj_rows(const phc_proj_rows_t* args /* host */, void* stream);
 
 /* The getup task's episode draws on the device (csrc/phc_getup.hip, per-env code and the rules in full csrc/phc_getup.h; additions to ABI 37, which stays 37):
  * `+env.task_rng=device`.  phc_getup_assign is the device form of HumanoidImGetup._reset_envs(reset_buf.nonzero()) up to the reset launches -- same rules as

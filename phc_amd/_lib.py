@@ -102,7 +102,7 @@ class RenderScene(C.Structure):
     _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("body_state", c_p), ("capsules", c_p), ("num_capsules", c_i32),
                 ("num_shape_blocks", c_i32), ("capsule_stride", c_i64), ("env_shape", c_p), ("markers", c_p), ("num_markers", c_i32),
                 ("marker_radius", c_f), ("palette", (c_f * 3) * RENDER_PALETTE), ("marker_color", c_f * 3), ("ground_color", (c_f * 3) * 2),
-                ("sky_color", c_f * 3), ("light_dir", c_f * 3), ("ambient", c_f), ("diffuse", c_f)]
+                ("sky_color", c_f * 3), ("light_dir", c_f * 3), ("ambient", c_f), ("diffuse", c_f), ("marker_radii", c_p), ("marker_colors", c_p)]
 
 
 RENDER_MESH_ID = 2000            # PHC_RENDER_MESH_ID
@@ -135,6 +135,27 @@ class PushArgs(C.Structure):
     _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("num_listed", c_i32), ("pause_lo", c_i32), ("pause_hi", c_i32), ("duration", c_i32),
                 ("direction", c_i32), ("force_lo", c_f), ("force_hi", c_f), ("key", C.c_uint64), ("env_offset", c_i64), ("bodies", c_p),
                 ("progress_buf", c_p), ("remaining", c_p), ("countdown", c_p), ("body", c_p), ("k", c_p), ("started", c_p), ("force", c_p)]
+
+
+PROJ_MAX_SLOTS, PROJ_MAX_SHAPES = 4, 64   # PHC_PROJ_MAX_SLOTS, PHC_PROJ_MAX_SHAPES
+
+
+class ProjArgs(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("num_bodies", c_i32), ("num_shapes", c_i32), ("num_listed", c_i32), ("count", c_i32), ("pause_lo", c_i32),
+                ("pause_hi", c_i32), ("life_steps", c_i32), ("substeps", c_i32), ("dt", c_f), ("gravity_z", c_f), ("radius", c_f), ("restitution", c_f),
+                ("friction", c_f), ("mass_lo", c_f), ("mass_hi", c_f), ("speed_lo", c_f), ("speed_hi", c_f), ("dist_lo", c_f), ("dist_hi", c_f),
+                ("elev_lo", c_f), ("elev_hi", c_f), ("key", C.c_uint64), ("env_offset", c_i64), ("bodies", c_p), ("capsules", c_p), ("owner", c_p),
+                ("body_com", c_p), ("body_inv_mass", c_p), ("body_inv_inertia", c_p), ("rigid_body_state", c_p), ("progress_buf", c_p), ("life", c_p),
+                ("countdown", c_p), ("thrown", c_p), ("hits", c_p), ("last_hit", c_p), ("k", c_p), ("pos", c_p), ("vel", c_p), ("mass", c_p),
+                ("force", c_p), ("torque", c_p)]
+
+
+PROJ_MAX_ROWSETS, PROJ_SNAPSHOT, PROJ_SELECT = 8, 0, 1   # PHC_PROJ_MAX_ROWSETS, PHC_PROJ_SNAPSHOT, PHC_PROJ_SELECT
+
+
+class ProjRows(C.Structure):
+    _fields_ = [("num_envs", c_i32), ("count", c_i32), ("num_sets", c_i32), ("mode", c_i32), ("last_hit", c_p), ("base", c_p * PROJ_MAX_ROWSETS),
+                ("shadow", c_p * PROJ_MAX_ROWSETS), ("width", c_i32 * PROJ_MAX_ROWSETS)]
 
 
 class GetupArgs(C.Structure):
@@ -274,6 +295,8 @@ _SIGNATURES = {
     "phc_render_mesh": ([P(RenderScene), P(RenderMeshes), P(Camera), c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p], c_i32),
     "phc_eval_accumulate": ([P(MotionLib), P(EvalArgs), c_p], c_i32),
     "phc_push_advance": ([P(PushArgs), c_p], c_i32),
+    "phc_proj_advance": ([P(ProjArgs), c_p], c_i32),
+    "phc_proj_rows": ([P(ProjRows), c_p], c_i32),
 }
 # Optional symbols: typed when the library has them.  An older build of the same ABI selected with PHC_AMD_LIB (an A/B baseline) lacks them and still loads; a
 # caller that needs one fails on the missing attribute.

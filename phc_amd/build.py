@@ -33,6 +33,8 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #     bit-equal to the host build of phc_obs_aug.h; the device's logf / sinf / cosf / sqrtf are the only difference of a noised element.
 #   motion recording (phc_record.hip): like phc_obs_aug.hip -- no contraction, no fast-math: its headers, counters and copied floats are bit-equal to the host
 #     build of phc_record.h; the root's exp map and the robots' axis x angle rows differ by the device's elementary functions alone.
+#   thrown projectiles (phc_proj.hip): like the push schedule -- no contraction, no fast-math: its decisions and floats follow the host build of phc_proj.h; the
+#     sinf / cosf of a throw are the only difference.
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_kernels_plain.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_sim_plain.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_render_mesh.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
@@ -40,8 +42,8 @@ SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_
            "phc_clip.hip": ["-ffp-contract=off"], "phc_clip_real.hip": ["-ffp-contract=off"], "phc_teleop.hip": ["-ffp-contract=off"],
            "phc_stream.hip": ["-ffp-contract=off"], "phc_distill.hip": ["-ffp-contract=off"],
            "phc_fit.hip": ["-ffp-contract=off"], "phc_getup.hip": ["-ffp-contract=off"],
-           "phc_obs_aug.hip": ["-ffp-contract=off"], "phc_record.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
+           "phc_obs_aug.hip": ["-ffp-contract=off"], "phc_record.hip": ["-ffp-contract=off"], "phc_proj.hip": ["-ffp-contract=off"]}
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_proj.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

@@ -24,6 +24,25 @@ __device__ __forceinline__ int group_or(int v) {
     for (int m = 16; m < G; m <<= 1) v |= __shfl_xor(v, m, G);
     return v;
 }
+// Minimum over the G lanes of an env's group, result in every lane: the same butterfly.  Every lane of the group must be active -- a DPP operand read
+// from a lane that EXEC has switched off is 0, which the sum ignores and the minimum does not.  (fminf: no NaN operands expected.)
+template <int G>
+__device__ __forceinline__ float group_min(float v) {
+    v = fminf(v, __int_as_float(dpp_i<0xB1>(__float_as_int(v))));
+    v = fminf(v, __int_as_float(dpp_i<0x4E>(__float_as_int(v))));
+    v = fminf(v, __int_as_float(dpp_i<0x141>(__float_as_int(v))));
+    v = fminf(v, __int_as_float(dpp_i<0x140>(__float_as_int(v))));
+#pragma unroll
+    for (int m = 16; m < G; m <<= 1) v = fminf(v, __shfl_xor(v, m, G));
+    return v;
+}
+template <int G>
+__device__ __forceinline__ int group_min(int v) {
+    v = min(v, dpp_i<0xB1>(v)); v = min(v, dpp_i<0x4E>(v)); v = min(v, dpp_i<0x141>(v)); v = min(v, dpp_i<0x140>(v));
+#pragma unroll
+    for (int m = 16; m < G; m <<= 1) v = min(v, __shfl_xor(v, m, G));
+    return v;
+}
 // The value that lane `src` (0 .. G-1) of the env's group holds, in every lane of the group.
 template <int G>
 __device__ __forceinline__ float group_bcast(float v, int src) { return __shfl(v, src, G); }

@@ -51,9 +51,9 @@ __global__ void __launch_bounds__(RD_THREADS) k_render(phc_render_scene_t sc, Re
         } else {
             const int m = i - S;
             c = ld3(sc.markers + ((int64_t)env * M + m) * 3);
-            r = sc.marker_radius;
+            r = sc.marker_radii ? sc.marker_radii[m] : sc.marker_radius;             // (per-marker radius / colour: nullable, see include/phc_amd.h)
             R = r > 0.0f ? r : -1.0f;
-            col = ld3(sc.marker_color);
+            col = sc.marker_colors ? ld3(sc.marker_colors + 3 * m) : ld3(sc.marker_color);
             id = PHC_RENDER_MARKER_ID + m;
         }
         P.p0[i] = make_float4(c.x, c.y, c.z, r);

@@ -440,6 +440,14 @@ class HumanoidIm:
         self._push = None
         if cfg.get("perturb", None):
             self._check_wrench_supported("perturb")
+        self._proj_shadow = None                    # phc_sim_state_t over the shadow tensors of a task with projectiles (_allocate_buffers)
+        self._proj = None                           # thrown projectiles `+projectile.*` (phc_amd/projectile.py): their impacts reach the stepper as wrenches too
+        if cfg.get("projectile", None):
+            if cfg.get("perturb", None):
+                raise ValueError("+perturb.* together with +projectile.*: one force / torque buffer pair reaches the stepper's launch")
+            self._check_wrench_supported("projectile")
+            from ...projectile import ProjectileOptions
+            ProjectileOptions(cfg["projectile"], list(self._body_names), self.dt)   # (the option checks, tunnelling included, before any device work)
 
     # ---- host phase: domain randomisation (`domain_rand=h1_dr`; phc_amd/domain_rand.py): refusals and the sampler; its tensors are made with the task's ----
     def _setup_domain_rand(self):
@@ -449,6 +457,8 @@ class HumanoidIm:
             return
         if self.cfg.get("perturb", None):
             raise NotImplementedError("domain_rand with +perturb.*: the stepper has no launch with both external wrenches and per-env physics")
+        if self.cfg.get("projectile", None):
+            raise NotImplementedError("domain_rand with +projectile.*: the stepper has no launch with both external wrenches and per-env physics")
         if self.has_shape_variation:
             raise NotImplementedError("domain_rand with robot.has_shape_variation: the env-shape blocks of the model carry either body shapes or DR variants")
         if int(self._sim_params.lane_mapping) == 3:
@@ -514,6 +524,18 @@ class HumanoidIm:
             # (`+perturb.rng=device`: one launch per step, capturable; the ranks of a multi-GPU run draw disjoint streams from one seed)
             self._push = make_schedule(pcfg, N, list(self._body_names), self.dt, dev, default_seed=int(self.cfg.get("seed", 0)),
                                        env_offset=int(self.cfg.get("rank", os.environ.get("RANK", 0))) * N)
+        jcfg = self.cfg.get("projectile", None)
+        if jcfg:
+            from ...projectile import ProjectileSchedule
+            self._proj = ProjectileSchedule(jcfg, N, self.model, self._rigid_body_state, self.dt, dev, gravity_z=float(self._sim_params.gravity_z),
+                                            friction=float(self._sim_params.friction), default_seed=int(self.cfg.get("seed", 0)),
+                                            env_offset=int(self.cfg.get("rank", os.environ.get("RANK", 0))) * N)
+            # the shadow copies of the simulator tensors and the phc_sim_state_t over them (see _physics_step): made here, with the task's buffers, so that no
+            # allocation can fall into a captured step
+            sim = [self._root_states, self._dof_state, self._rigid_body_state, self._contact_forces, self.dof_force_tensor, self._pd_target]
+            sim += [self.vec_sensor_tensor] if self.vec_sensor_tensor is not None else []
+            sh = self._proj.shadow_of(sim)
+            self._proj_shadow = abi.sim_state_struct(N, *sh[:6], force_sensor=sh[6] if len(sh) > 6 else None, env_shape=self._env_shape)
 
     # ---- device phase: action scaling (A1) + freeze masks (humanoid.py:1331-1409,1549-1554) ----
     def _setup_action_scaling(self):
@@ -639,6 +661,8 @@ class HumanoidIm:
                 self.random_occlu_idx = self._occl_mask.view(torch.bool)
         if self._res_action:
             self._sim_struct.pd_ref = abi.ptr(self.ref_dof_pos)
+            if self._proj_shadow is not None:   # (read-only: the shadow launch reads the task's reference pose)
+                self._proj_shadow.pd_ref = self._sim_struct.pd_ref
         self.ref_motion_cache = {}
         self._tab = [torch.from_numpy(t).to(dev) for t in self._up["tab"]]
         self._im_params = None
@@ -883,6 +907,8 @@ class HumanoidIm:
                 self._update_occl_training()
         if self._push is not None:   # (an env reset since the last step has progress 0: its push ends, a new pause is drawn)
             self._push.advance(self.progress_buf if self._push.capturable else self.progress_buf == 0)
+        if self._proj is not None:   # flight, collision test and impulses of this env step, from the body states the last step published
+            self._proj.advance(self.progress_buf)
         if self._dr is not None:     # control delay and velocity push (phc_dr_advance); `self.actions` stays the undelayed tensor
             self._dr.advance(self.actions.contiguous(), self.progress_buf)
 
@@ -907,6 +933,20 @@ class HumanoidIm:
         if self._dr is not None:        # per-env physics: the K-block model, the delayed actions
             L.check(self._lib.phc_sim_step_dr(self._dr.model_struct, self._sim_params, self._dr_sim_struct, self._dr.delayed_actions.data_ptr(), off.data_ptr(),
                                               scale.data_ptr(), self._freeze_mask.data_ptr(), self.control_freq_inv, self._dr.sim_dr, _stream()), "phc_sim_step_dr")
+            return
+        if self._proj is not None:
+            # Thrown projectiles.  Every env takes the launch the task takes without the group; a shadow copy of the simulator tensors takes
+            # phc_sim_step_wrench with the impulses of this step's hits (forces and torques held over the env step), and the envs a projectile struck take
+            # the shadow's rows (phc_proj_rows).  So an env that nothing struck is, bit for bit, the env of the same task without `+projectile` -- the
+            # wrench instantiation of the stepper differs from the plain one by fast-math rounding even with zero buffers -- at the price of a second
+            # stepper launch per env step.  Four launches, no host read: whole-step graphs stay.
+            self._proj.snapshot()
+            L.check(self._lib.phc_sim_step(self._model_struct, self._sim_params, self._sim_struct, a.data_ptr(), off.data_ptr(), scale.data_ptr(),
+                                           self._freeze_mask.data_ptr(), self.control_freq_inv, _stream()), "phc_sim_step")
+            L.check(self._lib.phc_sim_step_wrench(self._model_struct, self._sim_params, self._proj_shadow, a.data_ptr(), off.data_ptr(), scale.data_ptr(),
+                                                  self._freeze_mask.data_ptr(), self.control_freq_inv, self._proj.force.data_ptr(), self._proj.torque.data_ptr(),
+                                                  self.control_freq_inv, _stream()), "phc_sim_step_wrench")
+            self._proj.select()
             return
         if self._push is not None:      # a schedule: the same launch in every step, its force buffer zero between pushes
             wrench = (self._push.force.data_ptr(), None, self.control_freq_inv)
@@ -937,6 +977,8 @@ class HumanoidIm:
             raise NotImplementedError("apply_rigid_body_force_tensors on a task with domain_rand: the stepper has no launch with both")
         if self._push is not None:
             raise ValueError("apply_rigid_body_force_tensors on a task with a push schedule (+perturb.*): the two durations do not mix in one launch")
+        if self._proj is not None:
+            raise ValueError("apply_rigid_body_force_tensors on a task with thrown projectiles (+projectile.*): one force / torque buffer pair reaches the launch")
         self._check_wrench_supported("apply_rigid_body_force_tensors")
         if forces is None and torques is None:
             self._ext_pending = None
@@ -1060,6 +1102,8 @@ class HumanoidIm:
         state = {"reset_rng_counter": int(self._reset_rng_dev.item()), "reset_counter": int(self._reset_counter)}
         if hasattr(self._push, "state_dict"):   # `+perturb.rng=device`: a resumed run continues its pushes
             state["push_schedule"] = self._push.state_dict()
+        if self._proj is not None:              # `+projectile.*`: ... and its projectiles
+            state["projectile"] = self._proj.state_dict()
         if self.task_rng == "device":           # `+env.task_rng=device`: ... and the task's own draws
             state["task_rng"] = self._task_rng_state()
         return state
@@ -1095,6 +1139,13 @@ class HumanoidIm:
             else:
                 print(f"[phc_amd] push schedule state not restored: the checkpoint's is for {tuple(saved['state'].shape)[-1]} envs, this task has "
                       f"{self.num_envs}; the schedule starts afresh", flush=True)
+        saved = state.get("projectile")         # the projectiles: under the same rule
+        if saved is not None and self._proj is not None and not flags.test:
+            if self._proj.fits(saved):
+                self._proj.load_state_dict(saved)
+            else:
+                print(f"[phc_amd] projectile state not restored: the checkpoint's is for {tuple(saved['int'].shape)[-1]} envs, this task has "
+                      f"{self.num_envs}; the projectiles start afresh", flush=True)
         # the task's device draws: under the same rule (same num_envs, not in test mode)
         saved = state.get("task_rng")
         if saved is not None and self.task_rng == "device" and not flags.test:

@@ -1005,6 +1005,7 @@ class IMAmpAgent:
         self.obs = self.env_reset()
         self._init_amp_demo_buf()
 
+    _proj_seen = 0   # the projectiles' hit count at the last read (`projectile/hits` is the difference per epoch)
     _push_seen = 0   # the schedule's push count at the last read (`perturb/pushes` is the difference per epoch)
 
     def train_epoch(self):
@@ -1056,6 +1057,10 @@ class IMAmpAgent:
         if push is not None:   # `+perturb.*` (train() admits the device schedule only): pushes started during this epoch's rollout in THIS rank's envs -- one scalar read, no reduction over ranks
             total = int(push.pushes)
             info["perturb/pushes"], self._push_seen = total - self._push_seen, total
+        proj = getattr(self.task, "_proj", None)
+        if proj is not None:   # `+projectile.*`: impacts on bodies during this epoch's rollout in THIS rank's envs -- one scalar read
+            total = int(proj.hits)
+            info["projectile/hits"], self._proj_seen = total - self._proj_seen, total
         if self._trace is not None:   # `+learning.params.config.trace_minibatches=True`: every optimizer step's scalars, in order (a diagnostic)
             tr = torch.stack(self._trace).cpu() if self._trace else torch.zeros(0)
             info["minibatch_trace"] = {k: tr[:, j].tolist() for j, k in enumerate(self.INFO_KEYS)} if tr.numel() else {}
@@ -1076,7 +1081,7 @@ class IMAmpAgent:
                "disc/reward_std": info["disc_reward_std"], "rewards/returns": info["mean_return"],
                "rewards/mb_rewards": info["mean_mb_reward"], "rewards/body_pos": raw[0], "rewards/body_rot": raw[1], "rewards/lin_vel": raw[2], "rewards/ang_vel": raw[3],
                "rewards/power": raw[4]}
-        out.update({k: v for k, v in info.items() if k.startswith(("eval/", "perturb/"))})
+        out.update({k: v for k, v in info.items() if k.startswith(("eval/", "perturb/", "projectile/"))})
         return {k: float(v) for k, v in out.items()}
 
     def _log_train_info(self, scalars, output_dir):
@@ -1114,6 +1119,9 @@ class IMAmpAgent:
         self.init_train()
         if push is not None:
             self._push_seen = int(push.pushes)
+        proj = getattr(self.task, "_proj", None)
+        if proj is not None:
+            self._proj_seen = int(proj.hits)
         c = self.config
         save_freq, save_best_after = int(c.get("save_frequency", 0)), int(c.get("save_best_after", 100))
         save_intermediate = bool(c.get("save_intermediate", False))
@@ -1123,7 +1131,8 @@ class IMAmpAgent:
             if self.rank == 0 and log is not None:
                 log(f"epoch {self.epoch_num}: total_fps {info['total_fps']:.0f} step_fps {info['step_fps']:.0f} task_r {info['mean_task_reward']:.4f} "
                     f"disc_r {info['mean_disc_reward']:.4f} a_loss {info['actor_loss']:.4f} c_loss {info['critic_loss']:.4f} disc_loss {info['disc_loss']:.4f}"
-                    + (f" perturb/pushes {info['perturb/pushes']}" if "perturb/pushes" in info else ""))
+                    + (f" perturb/pushes {info['perturb/pushes']}" if "perturb/pushes" in info else "")
+                    + (f" projectile/hits {info['projectile/hits']}" if "projectile/hits" in info else ""))
             if output_dir is not None and save_freq > 0:
                 if self.epoch_num % min(50, save_best_after) == 0 and self.rank == 0:
                     os.makedirs(output_dir, exist_ok=True)
@@ -1137,6 +1146,8 @@ class IMAmpAgent:
                         info.update(eval_info)
                         if push is not None:   # (the sweep ran on the same schedule: its pushes are in `perturb_pushes`, not in the next epoch's count)
                             self._push_seen = int(push.pushes)
+                        if proj is not None:
+                            self._proj_seen = int(proj.hits)
             if output_dir is not None and self.rank == 0:
                 self._log_train_info(self.assemble_train_info(info), output_dir)
         return info

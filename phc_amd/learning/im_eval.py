@@ -218,6 +218,8 @@ def evaluate(agent, output_dir=None, log=print):
         rec = mrec if drec is None else _Recorders([drec, mrec])
     push = getattr(task, "_push", None)                         # `+perturb.*` (phc_amd/perturb.py): the sweep then runs under scheduled pushes
     pushes0 = int(push.pushes) if push is not None else 0
+    proj = getattr(task, "_proj", None)                         # `+projectile.*` (phc_amd/projectile.py): ... or under thrown projectiles
+    proj0 = (int(proj.thrown), int(proj.hits)) if proj is not None else (0, 0)
     failed = np.zeros(U, dtype=np.float64)                      # 1 where the clip terminated before its last frame
     per_clip = {k: np.zeros(U) for k in METRICS}                # metric value of every clip this rank evaluated ...
     have = {k: np.zeros(U) for k in METRICS}                    # ... and whether the clip has that metric
@@ -260,6 +262,8 @@ def evaluate(agent, output_dir=None, log=print):
                      "eval/mpjpel_succ": m_succ["mpjpe_l"], "eval/mpjpe_pa": m_succ["mpjpe_pa"]}
         if push is not None:
             eval_info["perturb_pushes"] = int(push.pushes) - pushes0   # pushes started during this rank's batches, all envs
+        if proj is not None:
+            eval_info["projectile_thrown"], eval_info["projectile_hits"] = int(proj.thrown) - proj0[0], int(proj.hits) - proj0[1]
     finally:
         if device_metrics:
             task.end_eval_accumulation()   # (an accumulation left open by an exception)

@@ -76,9 +76,10 @@ def capsule_table(models):
     return out.reshape(len(models), 8 * S)
 
 
-def scene_struct(capsules, num_envs, num_bodies, body_state, env_shape=None, markers=None, marker_radius=MARKER_RADIUS, style=None):
+def scene_struct(capsules, num_envs, num_bodies, body_state, env_shape=None, markers=None, marker_radius=MARKER_RADIUS, style=None, marker_radii=None,
+                 marker_colors=None):
     """phc_render_scene_t over device tensors: capsules float32 [K, 8 S] (capsule_table), body_state [N, NB, 13], env_shape int32 [N] or
-    None, markers float32 [N, M, 3] or None."""
+    None, markers float32 [N, M, 3] or None; marker_radii float32 [M] / marker_colors float32 [M, 3] or None (marker_radius / the style's colour for all)."""
     st = dict(STYLE, **(style or {}))
     s = L.RenderScene()
     s.num_envs, s.num_bodies = int(num_envs), int(num_bodies)
@@ -90,6 +91,11 @@ def scene_struct(capsules, num_envs, num_bodies, body_state, env_shape=None, mar
     s.markers = markers.data_ptr() if markers is not None else None
     s.num_markers = int(markers.shape[1]) if markers is not None else 0
     s.marker_radius = float(marker_radius)
+    for name, t, width in (("marker_radii", marker_radii, 1), ("marker_colors", marker_colors, 3)):
+        if t is not None and (markers is None or t.dtype != torch.float32 or t.numel() != width * int(markers.shape[1]) or not t.is_contiguous()):
+            raise ValueError(f"{name}: a contiguous float32 tensor of {width} value(s) per marker")
+    s.marker_radii = marker_radii.data_ptr() if marker_radii is not None else None
+    s.marker_colors = marker_colors.data_ptr() if marker_colors is not None else None
     for i in range(L.RENDER_PALETTE):
         s.palette[i][:] = PALETTE[i % len(PALETTE)]
     s.marker_color[:] = st["marker_color"]
@@ -125,13 +131,39 @@ def render_envs(task, env_ids, cameras, width, height, markers=True, depth=False
     skip the upload.  meshes: an uploaded render_mesh.MeshSet, drawn through phc_render_mesh in place of the capsules of its bodies."""
     caps = task_capsules(task) if capsules is None else capsules   # (held until the launch: the scene keeps raw pointers only)
     env_shape = task._env_shape if len(task.shape_models) > 1 else None
-    scene = scene_struct(caps, task.num_envs, task.num_bodies, task._rigid_body_state_reshaped, env_shape=env_shape,
-                         markers=task.ref_body_pos if markers else None)
+    marks, radii, colors = (task.ref_body_pos if markers else None), None, None
+    proj = getattr(task, "_proj", None)
+    if proj is not None:   # `+projectile.*`: the projectiles behind the reference markers, each with its own radius, a neutral grey (parked ones sit far below the ground)
+        marks, radii, colors = projectile_markers(marks, proj.pos, proj.opt.radius, cache=proj.marker_cache)   # (held until the launch: the scene keeps raw pointers only)
+    scene = scene_struct(caps, task.num_envs, task.num_bodies, task._rigid_body_state_reshaped, env_shape=env_shape, markers=marks, marker_radii=radii,
+                         marker_colors=colors)
     if meshes is not None:
         from . import render_mesh
         return render_mesh.render(scene, meshes, cameras, [int(e) for e in env_ids], width, height, depth=depth, hit_id=hit_id, device=task.device,
                                   lib=task._lib)
     return render(scene, cameras, [int(e) for e in env_ids], width, height, depth=depth, hit_id=hit_id, device=task.device, lib=task._lib)
+
+
+PROJECTILE_COLOR = (0.5, 0.5, 0.5)
+
+
+def projectile_markers(markers, pos, radius, marker_radius=MARKER_RADIUS, marker_color=None, cache=None):
+    """The marker list with the projectiles appended: markers [N, M, 3] or None, pos [P, N, 3] (ProjectileSchedule.pos) -> markers [N, M + P, 3], radii
+    [M + P], colours [M + P, 3].  Radii and colours are the same in every frame of a task: `cache` (a dict, ProjectileSchedule.marker_cache) keeps them on
+    the device per marker count, so a frame uploads nothing."""
+    M = 0 if markers is None else int(markers.shape[1])
+    P = int(pos.shape[0])
+    p = pos.permute(1, 0, 2)
+    marks = (p if markers is None else torch.cat([markers, p], dim=1)).contiguous()
+    base = tuple(STYLE["marker_color"] if marker_color is None else marker_color)
+    key = (M, P, float(radius), float(marker_radius), base)
+    if cache is None or key not in cache:
+        radii = torch.tensor([marker_radius] * M + [float(radius)] * P, dtype=torch.float32, device=pos.device)
+        colors = torch.tensor([list(base)] * M + [list(PROJECTILE_COLOR)] * P, dtype=torch.float32, device=pos.device)
+        if cache is None:
+            return marks, radii, colors
+        cache[key] = (radii, colors)
+    return (marks,) + cache[key]
 
 
 def tile(frames, cols):

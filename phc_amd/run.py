@@ -89,6 +89,8 @@ def play(agent, task, env, steps=300):
         motion_record.refuse_ranks(os.environ.get("WORLD_SIZE", "1"))
     mrec = motion_record.MotionRecorder(task, ropt["max_frames"], ropt["ref"]) if ropt is not None else None
     pushes0 = int(task._push.pushes) if getattr(task, "_push", None) is not None else 0
+    proj = getattr(task, "_proj", None)
+    proj0 = (int(proj.thrown), int(proj.hits)) if proj is not None else (0, 0)
     obs = env.reset()
     if mrec is not None:
         mrec.begin_play()
@@ -119,6 +121,8 @@ def play(agent, task, env, steps=300):
     out = {"episodes": int(lens.numel()), "mean_episode_length": float(lens.mean()), "mean_episode_reward": float(rews.mean()), "steps": steps}
     if getattr(task, "_push", None) is not None:   # `+perturb.*` (phc_amd/perturb.py): pushes started during the rollout, all envs
         out["perturb_pushes"] = int(task._push.pushes) - pushes0
+    if proj is not None:   # `+projectile.*` (phc_amd/projectile.py): projectiles thrown and impacts on bodies during the rollout, all envs
+        out["projectile_thrown"], out["projectile_hits"] = int(proj.thrown) - proj0[0], int(proj.hits) - proj0[1]
     if mrec is not None:
         out.update(mrec.close())
         mrec.export(ropt["path"], log=None)
