@@ -1310,6 +1310,30 @@ typedef struct {
 int64_t phc_fit_scratch_bytes(int64_t num_frames, int32_t num_clips, int32_t num_bodies_ext);
 int32_t phc_fit_iterate(const phc_fit_args_t* args /* host; pointers device memory except clip_start_host */, int32_t iterations, void* stream);
 
+/* Keypoint fit of the all-spherical SMPL family on the device (csrc/phc_fit_sph.hip, per-lane code csrc/phc_fit_sph.h over csrc/phc_fit.h; an addition to
+ * ABI 37, which stays 37): `iterations` trips of the loop of `fit_keypoint_clips` (phc_amd/utils/fit_keypoints.py) for C concatenated clips at once, fp32
+ * throughout.  It takes phc_fit_args_t as it is, read for spherical joints: with ND = 3 (NB - 1), `dof`, `dof_m`, `dof_v` are [F, ND] -- body b's rotation
+ * vector in its parent's frame at columns 3 (b - 1) .. 3 (b - 1) + 2 --, `range` is [ND, 2], the scratch rows are ND floats wide, `axis` is not read and may
+ * be null, and num_ext is 0.  One trip is
+ *   1. FK: R_0 = exp(root_rot), p_0 = root_trans_offset + root_off[c]; R_b = R_parent rest_b exp(rot_b), p_b = p_parent + R_parent offset_b;
+ *   2. loss_c = mean_{t, m} |p[match_body[m]] - target[:, match_slot[m]]| + 0.01 mean(dof^2) (the regulariser over T_c ND values) -> loss[c];
+ *   3. its analytic gradient: for a joint, with tau the torque of its subtree's matched entries in the joint's own frame,
+ *      (tau + B r x tau + C r x (r x tau)) / (T_c M) + 0.02 r / (T_c ND) (the transposed right Jacobian of exp at r); the root rotation vector and root_off as
+ *      in phc_fit_iterate;
+ *   4. Adam with the clip's own step counter, as phc_fit_iterate; every component of dof clamped to `range`;
+ *   5. dof smoothed along the clip's own frames by the normalised 5-tap gaussian of sigma 0.75 with replicate padding.  The root rotation is neither clamped
+ *      nor smoothed.
+ * Two launches per trip behind phc_fit_iterate's table launch, on `stream`, capturable in a graph: (a) one block per tile of 8 frames, a group of 32 lanes a
+ * frame, a lane a body: steps 1-4 into the scratch rows, the partial sums per tile; (b) step 5 from `scratch` into `dof`, and per clip the partial sums added
+ * in tile order, root_off's Adam step, loss[c] and step[c].  The sums' orders are phc_fit_iterate's: a clip's state after any number of trips has the same
+ * bits alone, first, last or between other clips, and iterations = a then = b give the bits of a + b.  iterations == 0 checks the arguments and launches
+ * nothing; a refused call writes nothing.  phc_fit_sph_scratch_bytes(F, C, NB): negative F, C < 1 or NB outside [1, 32]: PHC_EINVAL.
+ * The checks are phc_fit_iterate's (with `axis` exempt from the null check and the scratch at least phc_fit_sph_scratch_bytes), then PHC_EUNSUPPORTED for
+ * num_bodies > 32 (no all-spherical model above 32 bodies ships: there is no 64-lane instantiation) and for num_ext != 0; num_matched > PHC_FIT_MAX_MATCHED is
+ * PHC_EUNSUPPORTED as there.  Whatever the device arrays hold, no lane reads or writes outside the arrays' stated sizes. */
+int64_t phc_fit_sph_scratch_bytes(int64_t num_frames, int32_t num_clips, int32_t num_bodies);
+int32_t phc_fit_sph_iterate(const phc_fit_args_t* args /* host; pointers device memory except clip_start_host */, int32_t iterations, void* stream);
+
 /* ---- Recording the simulated motion (csrc/phc_record.hip, per-lane code and the rules csrc/phc_record.h; an addition to ABI 37, which stays 37) ------------
  * phc_motion_record: ONE launch per call, behind the post-physics launch on the same stream.  For every env i it appends one frame row to env i's block
  * [cap, W] of the caller-owned `frames` [N, cap, W] (fp32) and one header row to `header` [N, cap, 4] (int32).  With NB simulated bodies, E extended

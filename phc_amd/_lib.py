@@ -321,6 +321,8 @@ _OPTIONAL_SIGNATURES = {
     "phc_mse_loss": ([c_p, c_i32, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p], c_i32),
     "phc_fit_scratch_bytes": ([c_i64, c_i32, c_i32], c_i64),
     "phc_fit_iterate": ([P(FitArgs), c_i32, c_p], c_i32),
+    "phc_fit_sph_scratch_bytes": ([c_i64, c_i32, c_i32], c_i64),
+    "phc_fit_sph_iterate": ([P(FitArgs), c_i32, c_p], c_i32),
     "phc_getup_assign": ([P(GetupArgs), c_p], c_i32),
     "phc_refresh_body_state_masked": ([P(Model), P(SimState), c_p, c_p], c_i32),
     "phc_im_reset_from_state_masked": ([P(Model), P(MotionLib), P(ImParams), P(SimState), P(ImBuffers), c_p, c_p], c_i32),

@@ -28,6 +28,7 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #     (phc_distill.h) operation by operation.
 #   keypoint-stream tracking (phc_stream.hip): like phc_teleop.hip -- its fp64 filter sums and its ring counters follow the host build of phc_stream.h.
 #   retargeting fit (phc_fit.hip): fp32, no contraction, no fast-math -- its sums, Adam step and step counters follow the host build of phc_fit.h; the device's sin / cos / sqrt are its only difference.
+#     phc_fit_sph.hip (the spherical-joint keypoint fit over the same per-lane pieces) is compiled with the same flags, against the host build of phc_fit_sph.h.
 #   getup draws (phc_getup.hip): like the push schedule -- its draws, kinds and slots are bit-equal to the host build of phc_getup.h.
 #   observation noise / dropout / occlusion draws (phc_obs_aug.hip): like phc_fit.hip -- no contraction, no fast-math: its draws, counters and dropout decisions are
 #     bit-equal to the host build of phc_obs_aug.h; the device's logf / sinf / cosf / sqrtf are the only difference of a noised element.
@@ -41,9 +42,9 @@ SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_
            "phc_push.hip": ["-ffp-contract=off"], "phc_sim_dr.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_dr.hip": ["-ffp-contract=off"],
            "phc_clip.hip": ["-ffp-contract=off"], "phc_clip_real.hip": ["-ffp-contract=off"], "phc_teleop.hip": ["-ffp-contract=off"],
            "phc_stream.hip": ["-ffp-contract=off"], "phc_distill.hip": ["-ffp-contract=off"],
-           "phc_fit.hip": ["-ffp-contract=off"], "phc_getup.hip": ["-ffp-contract=off"],
+           "phc_fit.hip": ["-ffp-contract=off"], "phc_fit_sph.hip": ["-ffp-contract=off"], "phc_getup.hip": ["-ffp-contract=off"],
            "phc_obs_aug.hip": ["-ffp-contract=off"], "phc_record.hip": ["-ffp-contract=off"], "phc_proj.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_proj.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_fit_sph.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_proj.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

@@ -44,6 +44,14 @@ __global__ __launch_bounds__(FIT_BLOCK) void k_fit_setup(phc_fit_args_t a, int t
     if (threadIdx.x == 0) s.tile_start[a.num_clips] = s_carry;
 }
 
+// k_fit_setup for the fits of other translation units (phc_fit_sph.hip): the same launch, the same table.
+namespace phc {
+hipError_t fit_launch_setup(const phc_fit_args_t& a, int tf, hipStream_t st) {
+    hipLaunchKernelGGL(k_fit_setup, dim3(1), dim3(FIT_BLOCK), 0, st, a, tf);
+    return hipGetLastError();
+}
+}  // namespace phc
+
 template <int G>
 __global__ __launch_bounds__(FIT_BLOCK) void k_fit_frames(phc_fit_args_t a) {
     constexpr int TF = FIT_BLOCK / G;
