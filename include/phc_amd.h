@@ -1383,6 +1383,56 @@ typedef struct {
 int32_t phc_motion_record_width(int32_t num_bodies, int32_t num_ext, int32_t num_dof, int32_t flags);
 int32_t phc_motion_record(const phc_model_t* model /* host */, const phc_motion_record_args_t* args /* host */, void* stream);
 
+/* ---- Video output: baseline JPEG scans of device frames (csrc/phc_jpeg.hip, per-block / per-segment code, the worst-case derivation and the scratch layout
+ * csrc/phc_jpeg.h; additions to ABI 37, which stays 37) -------------------------------------------------------------------------------------------------------
+ * `+render.format=avi` (phc_amd/video.py): the renderer's frames leave the device as the entropy-coded scans of a Motion-JPEG stream instead of 1.2 MB of
+ * pixels each.  One call codes F frames rgba u8 [F, H, W, 4] (rows row_stride bytes apart, frames frame_stride bytes apart; alpha is ignored) into F
+ * contiguous byte runs out[f * out_stride .. + length[f]): the complete scan of frame f, from the first entropy-coded byte to the last, RSTn markers included.
+ * The host puts the frame header (SOI .. SOS: phc_amd/video.py jpeg_header) in front and EOI behind.  The stream is ISO/IEC 10918-1 baseline sequential, 8-bit,
+ * three components, one interleaved scan:
+ *   colour     JFIF full-range BT.601 of 8-bit R, G, B:  Y = 0.299 R + 0.587 G + 0.114 B,  Cb = -0.168735892 R - 0.331264108 G + 0.5 B + 128,
+ *              Cr = 0.5 R - 0.418687589 G - 0.081312411 B + 128; level shift 128.  The frame is extended to multiples of 16 by replicating its last column and
+ *              row (SOF0 carries the true size); chroma is 4:2:0, a sample = the mean of its 2 x 2 pixel group of the extended frame.  The MCU is 16 x 16
+ *              pixels: Y00 Y01 Y10 Y11 Cb Cr, MCUs in raster order.
+ *   transform  the orthonormal 8 x 8 DCT-II of A.3.3, S(v,u) = C(u) C(v) / 4 sum_y sum_x s(y,x) cos((2x+1) u pi / 16) cos((2y+1) v pi / 16), in fp32 as two
+ *              passes of eight-term sums.  Quantisation: sign(S) floor(|S| / q + 0.5) with the caller's table entry q, in zigzag order (Figure A.6); the
+ *              result is clamped to [-1023, 1023] (DC: [-1024, 1023]), which 8-bit input never reaches.
+ *   qtab       u8 [2][64], HOST memory, zigzag order as DQT carries them: luminance, chrominance.  The caller scales Tables K.1 / K.2 (libjpeg's rule:
+ *              s = quality < 50 ? 5000 / quality : 200 - 2 quality; clamp((t s + 50) / 100, 1, 255)); the kernels have no notion of quality.
+ *   entropy    the typical Huffman tables K.3 - K.6 (the header emits them as DHT).  DC: the difference to the previous block of the same component, category
+ *              SSSS + SSSS extra bits; AC: run / size symbols, ZRL for every 16 zeros in front of a non-zero coefficient, EOB behind the last non-zero one unless
+ *              that is coefficient 63 (F.1.2).  A negative value's extra bits are those of value - 1.
+ *   restarts   a segment is restart_interval MCUs (the last one of a frame may be shorter; an interval above the frame's MCU count is one segment); DRI says
+ *              so.  The DC predictors are 0 at the start of every segment, its last byte is padded with 1-bits, every 0xFF byte of entropy-coded data is
+ *              followed by 0x00, and segment i, unless it is the frame's last, is followed by the marker RST(i mod 8).
+ * Segments are independent, so they are coded in parallel, each into a slot of worst-case size in `scratch`, and then moved to their places by a sum over the
+ * segment lengths: no atomics, the bytes depend on the input alone and repeats are byte-identical.  phc_jpeg_frame_bound is the most a frame can take (1660 bits
+ * per block, doubled for stuffing, + 2 per segment: phc_jpeg.h) and the least out_stride; no input makes a kernel write outside out [F, out_stride], length [F],
+ * coef and scratch [scratch_bytes].
+ * coef (nullable): i16 [F, 6 M, 64], M = ceil(W / 16) ceil(H / 16) -- the quantised coefficients in zigzag order, per component plane in raster block order:
+ * the Y plane's 4 M blocks (a grid 2 ceil(W / 16) wide), then Cb's M, then Cr's M.
+ * PHC_EINVAL before any device work for: args or rgba / qtab / out / length / scratch NULL, width or height outside 1 .. 65535, num_frames < 0, a quantiser entry
+ * of 0, restart_interval < 1, row_stride < 4 width or not a multiple of 4, frame_stride < height row_stride or not a multiple of 4, rgba not 4-byte or coef /
+ * scratch not 16-byte aligned, out_stride < phc_jpeg_frame_bound, scratch_bytes < phc_jpeg_scratch_bytes.  PHC_EUNSUPPORTED where a frame's bound passes 2^31 - 1
+ * (its offsets are 32-bit).  num_frames == 0 returns 0 without a launch.  The two size functions return PHC_EINVAL for sizes the call would refuse. */
+typedef struct {
+    int32_t num_frames;                       /* F */
+    int32_t width, height;                    /* W, H */
+    int32_t restart_interval;                 /* MCUs per segment */
+    int64_t row_stride, frame_stride;         /* bytes */
+    const uint8_t* rgba;
+    const uint8_t* qtab;                      /* host, [2][64] */
+    uint8_t* out;                             /* [F, out_stride] */
+    int64_t  out_stride;
+    int32_t* length;                          /* [F] out */
+    int16_t* coef;                            /* [F, 6 M, 64] out; nullable */
+    void*    scratch;
+    int64_t  scratch_bytes;
+} phc_jpeg_args_t;
+int64_t phc_jpeg_frame_bound(int32_t width, int32_t height, int32_t restart_interval);
+int64_t phc_jpeg_scratch_bytes(int64_t num_frames, int32_t width, int32_t height, int32_t restart_interval);
+int32_t phc_jpeg_encode(const phc_jpeg_args_t* args /* host */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,11 @@ class MotionRecordArgs(C.Structure):
                 ("len", c_p), ("seg", c_p), ("closed", c_p), ("dropped", c_p)]
 
 
+class JpegArgs(C.Structure):
+    _fields_ = [("num_frames", c_i32), ("width", c_i32), ("height", c_i32), ("restart_interval", c_i32), ("row_stride", c_i64), ("frame_stride", c_i64),
+                ("rgba", c_p), ("qtab", c_p), ("out", c_p), ("out_stride", c_i64), ("length", c_p), ("coef", c_p), ("scratch", c_p), ("scratch_bytes", c_i64)]
+
+
 _SIGNATURES = {
     "phc_abi_version": ([], c_i32),
     "phc_motion_state": ([P(MotionLib), c_i32] + [c_p] * 15, c_i32),
@@ -297,6 +302,9 @@ _SIGNATURES = {
     "phc_push_advance": ([P(PushArgs), c_p], c_i32),
     "phc_proj_advance": ([P(ProjArgs), c_p], c_i32),
     "phc_proj_rows": ([P(ProjRows), c_p], c_i32),
+    "phc_jpeg_frame_bound": ([c_i32, c_i32, c_i32], c_i64),
+    "phc_jpeg_scratch_bytes": ([c_i64, c_i32, c_i32, c_i32], c_i64),
+    "phc_jpeg_encode": ([P(JpegArgs), c_p], c_i32),
 }
 # Optional symbols: typed when the library has them.  An older build of the same ABI selected with PHC_AMD_LIB (an A/B baseline) lacks them and still loads; a
 # caller that needs one fails on the missing attribute.

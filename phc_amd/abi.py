@@ -419,6 +419,18 @@ def motion_record_args_struct(num_envs, num_bodies, num_ext, num_dof, cap, dt, *
     return a
 
 
+def jpeg_args_struct(num_frames, width, height, restart_interval, row_stride, frame_stride, out_stride, scratch_bytes, **arrays):
+    """phc_jpeg_args_t (phc_jpeg_encode): strides in bytes; `arrays` are rgba, qtab (HOST memory: uint8 [2, 64], zigzag order), out, length, scratch and
+    optionally coef, as torch tensors / numpy arrays (contiguous) or raw addresses (a strided view's first element)."""
+    a = L.JpegArgs()
+    a.num_frames, a.width, a.height, a.restart_interval = int(num_frames), int(width), int(height), int(restart_interval)
+    a.row_stride, a.frame_stride, a.out_stride, a.scratch_bytes = int(row_stride), int(frame_stride), int(out_stride), int(scratch_bytes)
+    assert set(arrays) <= {"rgba", "qtab", "out", "length", "scratch", "coef"}, sorted(arrays)
+    for name, x in arrays.items():
+        setattr(a, name, x if x is None or isinstance(x, int) else ptr(x))
+    return a
+
+
 def motion_record_width(num_bodies, num_ext, num_dof, ref=False):
     """W of a frame row (phc_motion_record_width): root_pos 3 | body quaternions 4 NB | pose_aa 3 (NB + E) | dof_pos D | root velocities 6 | time 1 | ref_body_pos 3 NB."""
     return 3 + 4 * int(num_bodies) + 3 * (int(num_bodies) + int(num_ext)) + int(num_dof) + 7 + (3 * int(num_bodies) if ref else 0)

@@ -36,6 +36,8 @@ LIB = os.path.join(HERE, "libphc_amd.so")
 #     build of phc_record.h; the root's exp map and the robots' axis x angle rows differ by the device's elementary functions alone.
 #   thrown projectiles (phc_proj.hip): like the push schedule -- no contraction, no fast-math: its decisions and floats follow the host build of phc_proj.h; the
 #     sinf / cosf of a throw are the only difference.
+#   video output (phc_jpeg.hip; off the training path): no contraction, no fast-math -- the transform is stated as fp32 sums in a fixed order, and the host
+#     build of phc_jpeg.h follows them operation by operation.
 SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_kernels_plain.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_sim.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_sim_wrench.hip": ["-ffast-math", "-fno-slp-vectorize"], "phc_sim_plain.hip": ["-ffast-math", "-fno-slp-vectorize"],
            "phc_learn.hip": ["-ffp-contract=off"], "phc_gemm.hip": ["-ffp-contract=off"], "phc_render.hip": [], "phc_render_mesh.hip": [], "phc_eval.hip": ["-ffp-contract=off"],
@@ -43,8 +45,9 @@ SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_
            "phc_clip.hip": ["-ffp-contract=off"], "phc_clip_real.hip": ["-ffp-contract=off"], "phc_teleop.hip": ["-ffp-contract=off"],
            "phc_stream.hip": ["-ffp-contract=off"], "phc_distill.hip": ["-ffp-contract=off"],
            "phc_fit.hip": ["-ffp-contract=off"], "phc_fit_sph.hip": ["-ffp-contract=off"], "phc_getup.hip": ["-ffp-contract=off"],
-           "phc_obs_aug.hip": ["-ffp-contract=off"], "phc_record.hip": ["-ffp-contract=off"], "phc_proj.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_fit_sph.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_proj.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
+           "phc_obs_aug.hip": ["-ffp-contract=off"], "phc_record.hip": ["-ffp-contract=off"], "phc_proj.hip": ["-ffp-contract=off"],
+           "phc_jpeg.hip": ["-ffp-contract=off"]}
+HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_fit_sph.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_proj.h", "phc_jpeg.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():

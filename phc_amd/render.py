@@ -6,6 +6,7 @@ appear as their capsule stand-ins; the H1 / G1 visual meshes are drawn only with
 directional light and, optionally, the reference bodies of the next frame as 5 cm spheres (humanoid_im.py:597-619 `_update_marker`).
 
     python -m phc_amd.run test=True ... +render.video=out [+render.envs=4 +render.width=640 +render.height=480 +render.markers=True +render.follow=True]
+                                        [+render.format=avi|both +render.quality=90]   (a Motion-JPEG file coded on the device: video.py)
 
 Nothing here runs unless `render.video` is set: the training and benchmark paths never import this module.
 """
@@ -203,18 +204,61 @@ def _mp4_backend():
         return None
 
 
+def video_options(rc):
+    """`render.format` (png, the default; avi; both) and `render.quality` (1 .. 100, default 90) of the `render.*` keys -> (format, quality)."""
+    fmt = str(rc.get("format", "png"))
+    if fmt not in ("png", "avi", "both"):
+        raise ValueError(f"render.format={fmt}: png, avi or both")
+    quality = int(rc.get("quality", 90))
+    if not 1 <= quality <= 100:
+        raise ValueError(f"render.quality={quality}: 1 .. 100")
+    return fmt, quality
+
+
 class VideoRecorder:
     """Numbered PNG frames `frame_000000.png ...` in `directory`, plus `<name>-<date>.mp4` at `fps` when imageio's ffmpeg backend is importable
-    (base_task.py:176-195,428-437: output/renderings/<exp_name>-<date>.mp4 at fps = 1 / dt)."""
+    (base_task.py:176-195,428-437: output/renderings/<exp_name>-<date>.mp4 at fps = 1 / dt).  `fmt` = avi writes `<name>-<date>.avi` (Motion-JPEG coded on
+    the device: phc_amd/video.py) in place of the PNGs and the mp4, both writes all of them; png is the default and imports nothing more."""
 
-    def __init__(self, directory, fps=30, name="video"):
+    def __init__(self, directory, fps=30, name="video", fmt="png", quality=90):
+        self.fmt, self.quality = video_options({"format": fmt, "quality": quality})
         self.dir = directory
         os.makedirs(directory, exist_ok=True)
         self.fps, self.name, self.count = int(fps), name, 0
-        self._imageio, self._writer = _mp4_backend(), None
+        self._imageio, self._writer = (_mp4_backend() if self.fmt != "avi" else None), None
         self.mp4_path = None
+        self.avi_path, self._avi, self._jpeg = None, None, None
 
     def add(self, frame):
+        if self.fmt != "png":
+            self._add_avi(frame[None])
+        if self.fmt != "avi":
+            self._add_png(frame)
+        self.count += 1
+
+    def add_many(self, frames):
+        """frames [n, H, W, 4] on the device: in avi mode one phc_jpeg_encode call for all of them."""
+        if self.fmt != "png":
+            self._add_avi(frames)
+        if self.fmt != "avi":
+            for a in frames.cpu():
+                self._add_png(a)
+                self.count += 1
+        else:
+            self.count += int(frames.shape[0])
+
+    def _add_avi(self, frames):
+        from . import video
+        if not isinstance(frames, torch.Tensor) or frames.device.type != "cuda":
+            raise RuntimeError("render.format=avi codes the frames with phc_jpeg_encode on a HIP device; these frames are in host memory (there is no CPU fallback)")
+        if self._avi is None:
+            self._jpeg = video.JpegEncoder()
+            self.avi_path = os.path.join(self.dir, f"{self.name}-{datetime.datetime.now().strftime('%Y-%m-%d-%H:%M:%S')}.avi")
+            self._avi = video.AviWriter(self.avi_path, int(frames.shape[2]), int(frames.shape[1]), self.fps)
+        for jpeg in self._jpeg.encode(frames, self.quality):
+            self._avi.add(jpeg)
+
+    def _add_png(self, frame):
         a = frame.cpu().numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
         write_png(os.path.join(self.dir, f"frame_{self.count:06d}.png"), a)
         if self._imageio is not None:
@@ -222,12 +266,14 @@ class VideoRecorder:
                 self.mp4_path = os.path.join(self.dir, f"{self.name}-{datetime.datetime.now().strftime('%Y-%m-%d-%H:%M:%S')}.mp4")
                 self._writer = self._imageio.get_writer(self.mp4_path, fps=self.fps, macro_block_size=None)
             self._writer.append_data(a[..., :3])
-        self.count += 1
 
     def close(self):
         if self._writer is not None:
             self._writer.close()
             self._writer = None
+        if self._avi is not None:
+            self._avi.close()
+            self._avi = None
 
 
 class TaskRecorder:
@@ -238,11 +284,16 @@ class TaskRecorder:
       render.markers draw the next frame's reference bodies (default flags.show_traj, as the reference)
       render.follow  cameras follow their env's root (default True; False: the first placement stays)
       render.meshes  path of the robot's MJCF: its visual meshes are drawn (phc_render_mesh) in place of the capsules of the bodies that carry one
-      render.mesh_color  asset (default: the MJCF rgba of each geom) or palette (the body palette)"""
+      render.mesh_color  asset (default: the MJCF rgba of each geom) or palette (the body palette)
+      render.format  png (default: numbered PNG frames), avi (one Motion-JPEG `<name>-<date>.avi`, coded on the device: phc_amd/video.py) or both
+      render.quality JPEG quality of the avi, 1 .. 100 (default 90)"""
 
     def __init__(self, task, rc):
         from .utils.flags import flags
         self.task = task
+        fmt, quality = video_options(rc)
+        if fmt != "png" and torch.device(task.device).type != "cuda":
+            raise RuntimeError(f"+render.format={fmt} launches phc_jpeg_encode on a HIP device; the task's tensors are on {task.device} (there is no CPU fallback)")
         self.k = max(1, min(int(rc.get("envs", 1)), task.num_envs))
         self.width, self.height = int(rc.get("width", 640)), int(rc.get("height", 480))
         self.markers = bool(rc.get("markers", flags.show_traj))
@@ -255,7 +306,8 @@ class TaskRecorder:
             from .render_mesh import task_mesh_set
             self.meshes = task_mesh_set(task, str(rc["meshes"]), str(rc.get("mesh_color", "asset")))
         rank = int(os.environ.get("RANK", "0"))        # (torchrun: every rank records its own envs into a directory of its own)
-        self.recorder = VideoRecorder(os.path.join(str(rc["video"]), f"rank{rank}") if rank else str(rc["video"]), fps=max(1, int(round(1.0 / task.dt))), name=str(task.cfg.get("exp_name", "video")))
+        self.recorder = VideoRecorder(os.path.join(str(rc["video"]), f"rank{rank}") if rank else str(rc["video"]), fps=max(1, int(round(1.0 / task.dt))), name=str(task.cfg.get("exp_name", "video")),
+                                      fmt=fmt, quality=quality)
 
     def record(self):
         t = self.task

@@ -63,6 +63,9 @@ def main(argv=None):
         else:
             info = play(agent, task, env, steps=int(cfg.get("games", 300)))
             task.close()   # (finishes a `+render.video` recording)
+            video = getattr(getattr(getattr(task, "_recorder", None), "recorder", None), "avi_path", None)   # `+render.format=avi|both` (phc_amd/video.py)
+            if video:
+                print("video:", video)
             if rank == 0:
                 print(info)
         if dist is not None:

@@ -3,7 +3,8 @@ scripts/vis/vis_motion_mj.py for headless hosts).
 
     python -m phc_amd.view_motion env.motion_file=<clips> [robot=... env=... sim=... control=...] +render.video=out \\
            [+replay.keys=[k1,k2] | +replay.clips=4] [+replay.compare=<other clips>] [+replay.fps=30] [+replay.frames=N] \\
-           [+render.meshes=<mjcf>] [+render.markers=True] [+render.follow=True] [+render.width=.. +render.height=..]
+           [+render.meshes=<mjcf>] [+render.markers=True] [+render.follow=True] [+render.width=.. +render.height=..] \\
+           [+render.format=avi|both +render.quality=90]     # one Motion-JPEG <name>-<date>.avi, coded on the device (phc_amd/video.py)
 
 Tiles: `replay.clips` = the first k clips of the library (default 1), or the clips named by `replay.keys`; one tile each.  Frame i shows the
 library's own get_motion_state at t = i / fps; a clip shorter than the longest holds its last frame.  The positions, rotations and velocities
@@ -168,7 +169,10 @@ def main(argv=None, task=None):
     if rc.get("meshes", None):
         from .render_mesh import task_mesh_set
         meshes = task_mesh_set(task, str(rc["meshes"]), str(rc.get("mesh_color", "asset")))
-    recorder = R.VideoRecorder(str(rc["video"]), fps=max(1, int(round(fps))), name=str(cfg.get("exp_name", "motion")))
+    fmt, quality = R.video_options(rc)
+    if fmt != "png" and torch.device(task.device).type != "cuda":
+        raise RuntimeError(f"+render.format={fmt} launches phc_jpeg_encode on a HIP device; the task's tensors are on {task.device} (there is no CPU fallback)")
+    recorder = R.VideoRecorder(str(rc["video"]), fps=max(1, int(round(fps))), name=str(cfg.get("exp_name", "motion")), fmt=fmt, quality=quality)
     cameras = [R.Camera() for _ in range(k)]
     placed = False
     err_sum = torch.zeros(k, dtype=torch.float64, device=dev)
@@ -209,11 +213,16 @@ def main(argv=None, task=None):
             img = render_mesh.render(scene, meshes, views, rows, width, height, device=dev, lib=task._lib)
         else:
             img = R.render(scene, views, rows, width, height, device=dev, lib=task._lib)
-        img = img.cpu()                                                          # the chunk's images, one copy
-        for f in range(n):
-            recorder.add(R.tile(img[f * tiles:(f + 1) * tiles], cols))
+        if fmt == "png":
+            img = img.cpu()                                                      # the chunk's images, one copy
+            for f in range(n):
+                recorder.add(R.tile(img[f * tiles:(f + 1) * tiles], cols))
+        else:                                                                    # tiled on the device, the whole chunk coded in one call; only the scans come back
+            recorder.add_many(torch.stack([R.tile(img[f * tiles:(f + 1) * tiles], cols) for f in range(n)]))
     recorder.close()
     out = {"frames": F, "clips": keys, "compare_mm": None}
+    if "format" in rc:
+        out["video"] = recorder.avi_path
     if len(libs) > 1:
         mm = (err_sum / err_cnt.clamp(min=1) * 1000.0).cpu().numpy()
         out["compare_mm"] = {key: float(v) for key, v in zip(keys, mm)}
