@@ -159,7 +159,9 @@ typedef struct {
                                          (tests/test_dynamics.py: dt-convergence with the switch on).  A ground-contact point that starts to touch in a
                                          lagged sub-step joins at the next fresh one (its impedance is not in the kept I^A).  0 = every sub-step fresh.
                                          The host side (HumanoidIm) sets 1 by default for contact_model 0 since round 6: pinned against the double-precision build
-                                         of this recursion (oracle/hostemu/hostemu64.cpp; tests/test_stepper_options.py). */
+                                         of this recursion (oracle/hostemu/hostemu64.cpp; tests/test_stepper_options.py), and that build -- like the HIP kernel
+                                         directly -- against an independent fp64 statement of the lagged scheme, oracle/aba_oracle.py
+                                         (tests/test_aba_oracle.py, tests/test_lag_regimes.py). */
     int32_t force_average;            /* 1 (solver.force_average): contact_force (S4) and dof_force (S5) are the MEANS over all sub-steps of the env step
                                          (what a power / contact reward integrates over the control interval); 0 = the last sub-step's values -- what Isaac
                                          Gym's tensors hold after simulate() with substeps > 1, as far as its documentation says (humanoid.py:185,193-194) */

@@ -249,6 +249,74 @@ def explicit_torque(model, st, target, kp_scale=1.0, kd_scale=1.0):
     return np.clip(tau, -model.dof_effort, model.dof_effort), np.where(sat, np.sign(tau) * model.dof_effort, sp), sat, tau
 
 
+def joint_drive(model, st, i, target, prm, dt, kp_scale=1.0, kd_scale=1.0, tau_hold=None, trace=None, limit_damper=True):
+    """The drive of body i's joint in one linearly-implicit sub-step, in joint coordinates: (tau, d, e) -- the explicit torque, the diagonal the joint adds to the
+    joint-space matrix (armature + implicit share of drive and limit) and the joint-limit error of a revolute joint (0.0: inside, or no limits).  Shared by
+    `accelerations` and oracle/aba_oracle.py.  `limit_damper` False (aba_oracle's lagged sub-steps only): an engaged limit is a spring with no damper and no implicit share."""
+    s, n = model.dof_start[i], st.nd[i - 1]
+    kp = model.dof_kp[s:s + n] * kp_scale
+    kd = model.dof_kd[s:s + n] * kd_scale
+    arm_ = model.dof_armature[s:s + n]
+    eff = model.dof_effort[s:s + n]
+    qd = st.qd[i - 1]
+    if n == 3:
+        qt = quat_from_rotvec(np.asarray(target[s:s + 3], dtype=np.float64))
+        err = quat_to_rotvec(quat_mul(quat_conj(st.q[i - 1]), qt))
+    else:
+        err = np.asarray(target[s:s + 1], dtype=np.float64) - st.theta[i - 1]
+    if trace is not None:   # what the effort clamp decides on: the spring term (implicit drive) or the whole explicit torque as it was held
+        trace["effort_ratio"][s:s + n] = kp * err / eff if prm["control_mode"] == 0 else tau_hold[3][s:s + n] / eff
+    if prm["control_mode"] == 1:   # explicit torque held over the simulate call
+        tau = np.array(tau_hold[0][s:s + n], dtype=np.float64)
+        d = arm_.copy()
+    elif prm["control_mode"] == 2:  # spring sampled per simulate call, damper continuous (implicit) unless saturated
+        if tau_hold[2][s]:
+            tau = np.array(tau_hold[1][s:s + n], dtype=np.float64)
+            d = arm_.copy()
+        else:
+            tau = tau_hold[1][s:s + n] - kd * qd
+            d = arm_ + dt * kd
+    else:
+        tau = np.clip(kp * err, -eff, eff) - (kd + dt * kp) * qd  # spring saturates, damping stays implicit
+        d = arm_ + dt * kd + dt * dt * kp
+    e = 0.0
+    if n == 1 and prm["limit_stiffness"] > 0:  # joint limit: implicit penalty spring-damper beyond [lo, hi]
+        lo, hi = model.dof_limits()
+        th = st.theta[i - 1]
+        e = (lo[s] - th) if th < lo[s] else ((hi[s] - th) if th > hi[s] else 0.0)
+        if e != 0.0:
+            kl, dl = prm["limit_stiffness"], prm["limit_damping"]
+            if limit_damper:
+                tau = tau + kl * e - (dl + dt * kl) * qd
+                d = d + dt * dl + dt * dt * kl
+            else:
+                tau = tau + kl * e
+    return tau, d, float(e)
+
+
+def penalty_point(prm, dt, p_i, w_i, v_i, arm, rad, rec=None):
+    """The penalty ground-contact law at one contact point of a body (origin p_i, velocities w_i / v_i; `arm` = R_i contact_pos, world axes): None when the point does not
+    push, else (arm of the contact location about the origin, its velocity uc, fn0, c_t, c_n) -- force F0 = (-c_t uc_x, -c_t uc_y, fn0) and implicit impedance
+    diag(c_t, c_t, c_n).  Shared by `accelerations` and oracle/aba_oracle.py; `rec`: the point's record of the branch witness."""
+    cn = prm["contact_stiffness"] * dt + prm["contact_damping"]
+    depth = rad - (p_i[2] + arm[2])
+    if depth <= 0:
+        return None
+    arm = arm - np.array([0, 0, rad])
+    uc = v_i + cross3(w_i, arm)
+    fn0 = prm["contact_stiffness"] * depth - cn * uc[2]
+    if rec is not None:
+        rec.update(fn0=float(fn0))
+    if fn0 <= 0:
+        return None
+    ut = np.hypot(uc[0], uc[1])
+    ct = min(prm["friction_viscous"], prm["friction"] * fn0 / (ut + 1e-6))
+    if rec is not None:
+        cone = prm["friction"] * fn0 / (ut + 1e-6) / prm["friction_viscous"]
+        rec.update(active=True, slip_speed=float(ut), cone_ratio=float(cone), friction="stick" if cone >= 1.0 else "slip")
+    return arm, uc, fn0, ct, cn
+
+
 def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, return_parts=False, tau_hold=None, nud_prev=None, cstate=None, trace=None):
     """Generalized accelerations nu_dot = [alpha0, a0, qdd_1..] of one implicit sub-step.  `nud_prev` (rigid contact model): the solution of
     the previous pass of this sub-step -- active set and friction cone are evaluated on the end-of-step velocities it predicts.
@@ -356,20 +424,10 @@ def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, ret
             if trace is not None:
                 rec = dict(point=int(k), body=int(i), depth=float(depth), kind="penetrating" if depth > 0 else "outside", active=False)
                 trace["contacts"].append(rec)
-            if depth <= 0:
+            pt = penalty_point(prm, dt, p[i], w[i], v[i], arm, rad, rec)
+            if pt is None:
                 continue
-            arm = arm - np.array([0, 0, rad])
-            uc = v[i] + cross3(w[i], arm)
-            fn0 = prm["contact_stiffness"] * depth - cn * uc[2]
-            if rec is not None:
-                rec.update(fn0=float(fn0))
-            if fn0 <= 0:
-                continue
-            ut = np.hypot(uc[0], uc[1])
-            ct = min(prm["friction_viscous"], prm["friction"] * fn0 / (ut + 1e-6))
-            if rec is not None:
-                cone = prm["friction"] * fn0 / (ut + 1e-6) / prm["friction_viscous"]
-                rec.update(active=True, slip_speed=float(ut), cone_ratio=float(cone), friction="stick" if cone >= 1.0 else "slip")
+            arm, uc, fn0, ct, _ = pt
             Cm = np.diag([ct, ct, cn])
             F0 = np.array([-ct * uc[0], -ct * uc[1], fn0])
             fcontact[i] += F0 - dt * Cm @ cross3(w[i], cross3(w[i], arm))
@@ -385,40 +443,7 @@ def accelerations(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, ret
     tau_all = [None] * nb
     dimp_all = [None] * nb
     for i in range(1, nb):
-        s, n = model.dof_start[i], st.nd[i - 1]
-        kp = model.dof_kp[s:s + n] * kp_scale
-        kd = model.dof_kd[s:s + n] * kd_scale
-        arm_ = model.dof_armature[s:s + n]
-        eff = model.dof_effort[s:s + n]
-        qd = st.qd[i - 1]
-        if n == 3:
-            qt = quat_from_rotvec(np.asarray(target[s:s + 3], dtype=np.float64))
-            err = quat_to_rotvec(quat_mul(quat_conj(st.q[i - 1]), qt))
-        else:
-            err = np.asarray(target[s:s + 1], dtype=np.float64) - st.theta[i - 1]
-        if trace is not None:   # what the effort clamp decides on: the spring term (implicit drive) or the whole explicit torque as it was held
-            trace["effort_ratio"][s:s + n] = kp * err / eff if prm["control_mode"] == 0 else tau_hold[3][s:s + n] / eff
-        if prm["control_mode"] == 1:   # explicit torque held over the simulate call
-            tau = np.array(tau_hold[0][s:s + n], dtype=np.float64)
-            d = arm_.copy()
-        elif prm["control_mode"] == 2:  # spring sampled per simulate call, damper continuous (implicit) unless saturated
-            if tau_hold[2][s]:
-                tau = np.array(tau_hold[1][s:s + n], dtype=np.float64)
-                d = arm_.copy()
-            else:
-                tau = tau_hold[1][s:s + n] - kd * qd
-                d = arm_ + dt * kd
-        else:
-            tau = np.clip(kp * err, -eff, eff) - (kd + dt * kp) * qd  # spring saturates, damping stays implicit
-            d = arm_ + dt * kd + dt * dt * kp
-        if n == 1 and prm["limit_stiffness"] > 0:  # joint limit: implicit penalty spring-damper beyond [lo, hi]
-            lo, hi = model.dof_limits()
-            th = st.theta[i - 1]
-            e = (lo[s] - th) if th < lo[s] else ((hi[s] - th) if th > hi[s] else 0.0)
-            if e != 0.0:
-                kl, dl = prm["limit_stiffness"], prm["limit_damping"]
-                tau = tau + kl * e - (dl + dt * kl) * qd
-                d = d + dt * dl + dt * dt * kl
+        tau, d, _ = joint_drive(model, st, i, target, prm, dt, kp_scale, kd_scale, tau_hold, trace)
         M[col(i), col(i)] += np.diag(d)
         rhs[col(i)] += tau
         tau_all[i], dimp_all[i] = tau, d
@@ -474,6 +499,12 @@ def substep(model, st, target, params, dt, kp_scale=1.0, kd_scale=1.0, tau_hold=
         for _ in range(1, max(1, int(prm["contact_iterations"]))):   # passes on active set and friction cone
             nud, parts = accelerations(model, st, target, prm, dt, kp_scale, kd_scale, return_parts=True, tau_hold=tau_hold, nud_prev=nud, cstate=cstate, trace=trace)
         parts["fcontact"] = rigid_contact_forces(model, parts, prm, dt, nud, cstate["active"]) + parts["fcontact"]
+    return integrate(model, st, nud, parts, prm, dt, trace)
+
+
+def integrate(model, st, nud, parts, prm, dt, trace=None):
+    """Semi-implicit Euler on the generalized accelerations `nud` = [alpha0, a0, qdd_1 ..] of one sub-step, with the root's angular damping and the joint-rate cap; returns
+    the applied joint torques (S5) and the net contact forces (S4).  `parts`: offs, tau, dimp (per body; with the armature), fcontact.  Shared with oracle/aba_oracle.py."""
     damp = 1.0 / (1.0 + dt * prm["angular_damping"])
     st.w0 = (st.w0 + dt * nud[0:3]) * damp
     st.v0 = st.v0 + dt * nud[3:6]

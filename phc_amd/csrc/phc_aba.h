@@ -673,7 +673,9 @@ PHC_HD void aba_body_init(AbaLane& L, const phc_model_t& m, const phc_sim_params
                 if (!lag) L.target.z = e != 0.f ? 1.f : 0.f;
             }
             L.tau_local = L.axis * tau;
-            L.dimp = v3(d, 0.f, 0.f);
+            // (a lagged sub-step solves with the kept D^-1, so the implicit share the joint feels -- what S5 subtracts in aba_integrate_joint -- is the fresh sub-step's:
+            //  it differs from `d` when a limit that was engaged then has released, tests/test_lag_regimes.py::test_released_limit_keeps_its_implicit_share)
+            if (!lag) L.dimp = v3(d, 0.f, 0.f);
             L.aw = mat_mul(R, L.axis);
             L.tau_w = L.aw * tau;
         }

@@ -69,16 +69,9 @@ def f32_params(prm):
     return d, float(prm.sim_dt), int(prm.substeps)
 
 
-@pytest.mark.parametrize("robot,control_mode", [("smpl_humanoid", 0), ("h1_humanoid", 0), ("h1_humanoid", 1), ("g1_humanoid", 2)])
-@pytest.mark.parametrize("height,anisotropic,reroot", [(0.95, False, True), (0.80, False, True), (0.80, True, True), (0.80, False, False), (3.0, False, True)])
-def test_double_precision_build_of_the_recursion_is_the_dense_scheme(robot, control_mode, height, anisotropic, reroot):
-    """oracle/hostemu/hostemu64.cpp -- the kernel's own per-lane recursion (re-rooted solver tree, linearly-implicit drives, penalty contact) compiled with every float a
-    double -- against the dense fp64 oracle, BOTH computing with the fp32-rounded parameters of the C struct: equal to 1e-9 (observed ~1e-14).  The recursion and the dense
-    M^-1 solve are the same scheme exactly; what separates the fp32 kernel from the oracle elsewhere in this file is rounding alone.  This build is also the
-    exact-arithmetic reference of the LAGGED scheme (tests/test_stepper_options.py), which has no dense form."""
-    import hostemu_util as hu
-    if robot != "smpl_humanoid" and (anisotropic or not reroot):
-        pytest.skip("SMPL-only variants")
+def dense_scheme_row(robot, control_mode, height, anisotropic, reroot, **opts):
+    """Model, three random states and parameters of a row of test_double_precision_build_of_the_recursion_is_the_dense_scheme (shared with tests/test_aba_oracle.py;
+    `opts`: further sim_params_struct keywords)."""
     model, _, _ = model_on(get_backend("hostemu"), name=robot, anisotropic=anisotropic, reroot=reroot)
     rng = np.random.default_rng(31)
     n = 3
@@ -89,9 +82,25 @@ def test_double_precision_build_of_the_recursion_is_the_dense_scheme(robot, cont
         lo, hi = model.dof_limits()
         dof[:, :, 0] = np.clip(dof[:, :, 0], lo + 0.05, hi - 0.05)
         target = np.clip(target, lo, hi).astype(F)
-    prm = abi.sim_params_struct(control_mode=control_mode) if not model.all_spherical else abi.sim_params_struct()
+    prm = abi.sim_params_struct(control_mode=control_mode, **opts) if not model.all_spherical else abi.sim_params_struct(**opts)
     if not model.all_spherical:
         prm.sim_dt = 1.0 / 200.0
+    return model, root, dof, target, prm
+
+
+@pytest.mark.parametrize("robot,control_mode", [("smpl_humanoid", 0), ("h1_humanoid", 0), ("h1_humanoid", 1), ("g1_humanoid", 2)])
+@pytest.mark.parametrize("height,anisotropic,reroot", [(0.95, False, True), (0.80, False, True), (0.80, True, True), (0.80, False, False), (3.0, False, True)])
+def test_double_precision_build_of_the_recursion_is_the_dense_scheme(robot, control_mode, height, anisotropic, reroot):
+    """oracle/hostemu/hostemu64.cpp -- the kernel's own per-lane recursion (re-rooted solver tree, linearly-implicit drives, penalty contact) compiled with every float a
+    double -- against the dense fp64 oracle, BOTH computing with the fp32-rounded parameters of the C struct: equal to 1e-9 (observed ~1e-14).  The recursion and the dense
+    M^-1 solve are the same scheme exactly; what separates the fp32 kernel from the oracle elsewhere in this file is rounding alone.  This build is also the
+    exact-arithmetic statement of the lane code's LAGGED scheme (tests/test_stepper_options.py), which has no dense form -- and is itself checked against the independent
+    recursion oracle/aba_oracle.py, lagged sub-steps included (tests/test_aba_oracle.py, tests/test_lag_regimes.py)."""
+    import hostemu_util as hu
+    if robot != "smpl_humanoid" and (anisotropic or not reroot):
+        pytest.skip("SMPL-only variants")
+    model, root, dof, target, prm = dense_scheme_row(robot, control_mode, height, anisotropic, reroot)
+    n = root.shape[0]
     out = hu.sim_step_f64(model, prm, root, dof, target, 2)
     dp, sim_dt, substeps = f32_params(prm)
     worst = 0.0

@@ -40,6 +40,24 @@ def test_inertia_lag_stays_close_to_the_fresh_scheme(backend, height):
     assert d_lag < 1.5 * d_fresh + 1e-4 and v_lag < 1.5 * v_fresh + 1e-2, (d_lag, d_fresh, v_lag, v_fresh)
 
 
+OPTIONS_ROWS = [("smpl_humanoid", 0, 0.95, False), ("smpl_humanoid", 0, 0.80, False), ("smpl_humanoid", 0, 0.80, True),
+                ("smpl_humanoid", 0, 3.0, False), ("h1_humanoid", 1, 0.85, False), ("g1_humanoid", 2, 0.70, False)]
+
+
+def options_row(model, lag, control_mode, height, n=6, **opts):
+    """States and parameters of a row of test_stepper_equals_the_double_precision_recursion (shared with tests/test_aba_oracle.py; `opts`: further sim_params_struct
+    keywords)."""
+    rng = np.random.default_rng(17)
+    if model.all_spherical:
+        root, dof, target = random_states(model, n, rng, height=height)
+        return root, dof, target, abi.sim_params_struct(inertia_lag=lag, **opts)
+    root, dof, target = random_states(model, n, rng, height=height, vel=0.5, pose=0.15)
+    lo, hi = model.dof_limits()
+    dof[:, :, 0] = np.clip(dof[:, :, 0], lo + 0.05, hi - 0.05)
+    target = np.clip(target, lo, hi).astype(F)
+    return root, dof, target, abi.sim_params_struct(**{**dict(inertia_lag=lag, control_mode=control_mode, sim_dt=1.0 / 200.0), **opts})
+
+
 @pytest.mark.parametrize("backend", BACKENDS)
 @pytest.mark.parametrize("lag", [0, 1])
 @pytest.mark.parametrize("robot,control_mode,height,anisotropic", [("smpl_humanoid", 0, 0.95, False), ("smpl_humanoid", 0, 0.80, False), ("smpl_humanoid", 0, 0.80, True),
@@ -47,24 +65,16 @@ def test_inertia_lag_stays_close_to_the_fresh_scheme(backend, height):
 def test_stepper_equals_the_double_precision_recursion(backend, lag, robot, control_mode, height, anisotropic):
     """Round 6: the LAGGED scheme pinned like the fresh one.  Reference = oracle/hostemu/hostemu64.cpp, the kernel's recursion at double precision -- which IS the dense
     fp64 oracle's scheme to 1e-12 with `inertia_lag` off (tests/test_dynamics.py::test_double_precision_build_of_the_recursion_is_the_dense_scheme) and states the lagged
-    scheme in exact arithmetic with it on (no dense form exists: the lagged result depends on the elimination order, oracle/hostemu/hostemu64.cpp).  The fp32 stepper
+    scheme in exact arithmetic with it on (no dense form exists, oracle/hostemu/hostemu64.cpp; that build is itself checked against the independent numpy recursion
+    oracle/aba_oracle.py on these rows and more in tests/test_aba_oracle.py, which also holds the HIP kernel to that oracle directly).  The fp32 stepper
     (host emulation and the HIP kernel) after one env step (2 x simulate x 2 sub-steps: sub-steps 2 and 4 lagged) from violent random states -- in the air, touching
     down, in contact; SMPL, anisotropic gains, H1 `pd`, G1 -- agrees with it at EXACTLY the tolerances `test_aba_matches_dense_oracle` holds the fresh scheme to."""
     import hostemu_util as hu
     from test_dynamics import check_step_against
     be = get_backend(backend)
     model, mstruct, keep = model_on(be, name=robot, anisotropic=anisotropic)
-    rng = np.random.default_rng(17)
     n = 6
-    if model.all_spherical:
-        root, dof, target = random_states(model, n, rng, height=height)
-        prm = abi.sim_params_struct(inertia_lag=lag)
-    else:
-        root, dof, target = random_states(model, n, rng, height=height, vel=0.5, pose=0.15)
-        lo, hi = model.dof_limits()
-        dof[:, :, 0] = np.clip(dof[:, :, 0], lo + 0.05, hi - 0.05)
-        target = np.clip(target, lo, hi).astype(F)
-        prm = abi.sim_params_struct(inertia_lag=lag, control_mode=control_mode, sim_dt=1.0 / 200.0)
+    root, dof, target, prm = options_row(model, lag, control_mode, height, n)
     out = run_step(be, model, mstruct, root, dof, target, prm, 2)
     ref = hu.sim_step_f64(model, prm, root, dof, target, 2)
     other = hu.sim_step_f64(model, abi.sim_params_struct(**{**{k: getattr(prm, k) for k in ("control_mode", "sim_dt")}, "inertia_lag": 1 - lag}), root, dof, target, 2)
