@@ -47,7 +47,6 @@ SOURCES = {"phc_kernels.hip": ["-fno-slp-vectorize", "-ffp-contract=off"], "phc_
            "phc_fit.hip": ["-ffp-contract=off"], "phc_fit_sph.hip": ["-ffp-contract=off"], "phc_getup.hip": ["-ffp-contract=off"],
            "phc_obs_aug.hip": ["-ffp-contract=off"], "phc_record.hip": ["-ffp-contract=off"], "phc_proj.hip": ["-ffp-contract=off"],
            "phc_jpeg.hip": ["-ffp-contract=off"]}
-HEADERS = ["phc_math.h", "phc_task.h", "phc_im.h", "phc_im_check.h", "phc_im_plain.h", "phc_task_kernel.h", "phc_aba.h", "phc_sim_kernel.h", "phc_sim_check.h", "phc_sim_plain.h", "phc_eval.h", "phc_group.h", "phc_rng.h", "phc_push.h", "phc_dr.h", "phc_clip.h", "phc_clip_real.h", "phc_teleop.h", "phc_stream.h", "phc_distill.h", "phc_fit.h", "phc_fit_sph.h", "phc_getup.h", "phc_obs_aug.h", "phc_record.h", "phc_proj.h", "phc_jpeg.h", "phc_render_ray.h", os.path.join("..", "..", "include", "phc_amd.h")]
 
 
 def _hipcc():
@@ -61,7 +60,8 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in list(SOURCES) + HEADERS)
+    headers = [f for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join("..", "..", "include", "phc_amd.h")]   # every header, so none can be forgotten
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in list(SOURCES) + headers)
 
 
 def build(force=False, verbose=False):

@@ -1,20 +1,14 @@
 """Shared by tests/test_clip_real_cpu.py and tests/test_clip_real_gpu.py: the host build of phc_amd/csrc/phc_clip_real.h (tests/clip_real_shim.cpp, g++), the
 three trees, the constructed robot clips, the oracle (the robot branch of `_run_clip_job`: the existing host path, never the code under test) with the
 conditions on its own intermediate values, and the field-by-field comparison at the tolerances that follow from "both sides compute in fp64 and round once"."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 
 from clip_util import ANG_FLOOR, EPS32, GUARD
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 LENGTHS = (3, 4, 8, 9, 16, 17, 18, 40)      # the filter radius (8) exceeds, meets and undershoots the clip; 3 frames: the dvs quirk at its edge
 FPS = (30, 60, 30, 60, 60, 30, 60, 30)
 TREES = ("h1", "g1", "chain")
@@ -30,13 +24,7 @@ BAD_ARGS = (("num_clips", 0, EINVAL), ("num_clips", -1, EINVAL), ("num_bodies", 
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="clip_real_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "clip_real_shim.so")
-    # the flags of phc_clip_real.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "clip_real_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("clip_real_shim.cpp", "phc_clip_real.hip")
     lib.clip_real_args_check_of.argtypes = [C.POINTER(L.ClipRealArgs)]
     lib.clip_real_args_check_of.restype = C.c_int
     lib.clip_real_scratch_bytes_of.argtypes = [C.c_longlong, C.c_int, C.c_int]

@@ -1,17 +1,13 @@
 """Shared by tests/test_clip_device_cpu.py and tests/test_clip_device_gpu.py: the host build of phc_amd/csrc/phc_clip.h (tests/clip_shim.cpp, g++), the
 constructed clips, the oracle (`process_clip` + float32 + `abi.pack_frames`: the existing host path, never the code under test) and the field-by-field
 comparison at the tolerances that follow from "both sides compute in fp64 and round once"."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD = 0x5A5A5A5A
 LENGTHS = (2, 3, 8, 9, 16, 17, 18, 40)      # the filter radius (8) exceeds, meets and undershoots the clip
 FPS = (30, 60, 30, 60, 60, 30, 60, 30)
@@ -29,13 +25,7 @@ BAD_ARGS = (("num_clips", 0, EINVAL), ("num_clips", -1, EINVAL), ("num_bodies", 
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="clip_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "clip_shim.so")
-    # the flags of phc_clip.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "clip_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("clip_shim.cpp", "phc_clip.hip")
     lib.clip_args_check_of.argtypes = [C.POINTER(L.ClipArgs)]
     lib.clip_args_check_of.restype = C.c_int
     lib.clip_scratch_bytes_of.argtypes = [C.c_longlong, C.c_int]

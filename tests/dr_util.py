@@ -1,14 +1,9 @@
 """TEST INFRASTRUCTURE for the domain-randomisation tests (tests/test_domain_rand_cpu.py, tests/test_domain_rand_gpu.py): the host build of
 phc_amd/csrc/phc_dr.h (tests/dr_shim.cpp, g++), a numpy-backed caller of it with the state layout of phc_dr_args_t, the cases (states, variants, amplitudes)
 both files use, and the oracle: the double-precision host stepper run once per env on that env's own statically modified model and friction."""
-import atexit
 import copy
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -16,8 +11,7 @@ import dyn_oracle as do
 import hostemu_util as hu
 import wrench_util as wu
 from phc_amd import abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 F = np.float32
 KEY = 0x1234ABCD5678EF01
 VEL_TOL, VEL_TOL_RIGID = 3e-3, 1e-2   # wrench_util.assert_standing
@@ -27,13 +21,7 @@ H1_OVER = ["robot=unitree_h1", "env=env_im_h1_phc", "sim=robot_sim", "control=ro
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="dr_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "dr_shim.so")
-    # the flags of phc_dr.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "dr_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("dr_shim.cpp", "phc_dr.hip")
     lib.dr_noise_u_batch.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
     lib.dr_noise_u_batch.restype = None
     lib.dr_shifted_target.argtypes = [C.c_float] * 4

@@ -1,7 +1,7 @@
 // A stand-alone run of the host build of phc_fit.h (tests/fit_shim.cpp) on the smallest batches, for the host sanitizers:
 //   g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -std=c++17 -I phc_amd/csrc tests/fit_asan_main.cpp -o fit_asan && ./fit_asan
 // Every array is a heap allocation of exactly its stated size, so a read or write one element outside is reported.  A 3-body chain with one extended body
-// (32-lane groups) and a 34-body chain (64-lane groups); clips of 1, 2 and 9 frames (a tile holds 8 or 4); 3 + 2 trips.  Not a pytest test; CPU only.
+// (32-lane groups) and a 34-body chain (64-lane groups); clips of 1, 2 and 9 frames (a tile holds 8 or 4); 3 + 2 trips.  Run by tests/test_fit_device_cpu.py; CPU only.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

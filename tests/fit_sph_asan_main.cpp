@@ -2,7 +2,7 @@
 //   g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -std=c++17 -I phc_amd/csrc tests/fit_sph_asan_main.cpp -o fit_sph_asan && ./fit_sph_asan
 // Every array is a heap allocation of exactly its stated size, so a read or write one element outside is reported; `axis` is null.  A 4-body tree (a chain
 // with a branch), a 1-body model (no joints) and a 32-body chain (every lane of the group, the longest ancestor mask); clips of 1, 2 and 9 frames (a tile
-// holds 8); 3 + 2 trips.  Not a pytest test; CPU only.
+// holds 8); 3 + 2 trips.  Run by tests/test_fit_keypoints_cpu.py; CPU only.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

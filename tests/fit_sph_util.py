@@ -2,19 +2,15 @@
 constructed batches, the runner over host or device memory with guard words behind every array, and the torch-fp64 single-iteration oracle (autograd +
 torch.optim.Adam + clamp + `gaussian_filter_time` on the statement of phc_amd/utils/fit_keypoints.py's docstring, written out here: never the code under test)
 with the fp32 rounding bound of tests/fit_util.py extended to rotation-vector joints."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import torch
 
 import fit_util as U
-from fit_util import EINVAL, EPS32, EUNSUPPORTED, GUARD_WORDS, LENGTHS, LR, ROOT, STATE, STEPS, collect, sub_case, zero_state   # noqa: F401
+from fit_util import EINVAL, EPS32, EUNSUPPORTED, GUARD_WORDS, LENGTHS, LR, STATE, STEPS, collect, sub_case, zero_state   # noqa: F401
+import host_build
 
 MODEL = ("parents", "offsets", "rest", "range", "match_body", "match_slot", "subtree")      # no `axis`: phc_fit_sph_iterate does not read it
 NAMES = ["chain4s", "smpl24", "smpl22"]
@@ -24,13 +20,7 @@ DIR = np.array([0.6, -0.64, 0.48])              # a unit vector: the direction o
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="fit_sph_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "fit_sph_shim.so")
-    # the flags of phc_fit_sph.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-Wno-comment", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "fit_sph_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("fit_sph_shim.cpp", "phc_fit_sph.hip")
     lib.fit_sph_args_check_of.argtypes = [C.POINTER(L.FitArgs), C.c_int]
     lib.fit_sph_args_check_of.restype = C.c_int
     lib.fit_sph_scratch_bytes_of.argtypes = [C.c_longlong, C.c_int, C.c_int]

@@ -1,18 +1,14 @@
 """Shared by tests/test_fit_device_cpu.py and tests/test_fit_device_gpu.py: the host build of phc_amd/csrc/phc_fit.h (tests/fit_shim.cpp, g++), the constructed
 batches, the runner over host or device memory with guard words behind every array, and the torch-fp64 single-iteration oracle (autograd +
 torch.optim.Adam + clamp + `gaussian_filter_time`: never the code under test) with the fp32 rounding bound it derives from the magnitudes it sums."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD = 0x5A5A5A5A
 GUARD_WORDS = 4
 EPS32 = 2.0 ** -24                              # half an fp32 ulp, relative: one rounding
@@ -27,13 +23,7 @@ LR = 0.02
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="fit_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "fit_shim.so")
-    # the flags of phc_fit.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-Wno-comment", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "fit_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("fit_shim.cpp", "phc_fit.hip")
     lib.fit_args_check_of.argtypes = [C.POINTER(L.FitArgs), C.c_int]
     lib.fit_args_check_of.restype = C.c_int
     lib.fit_scratch_bytes_of.argtypes = [C.c_longlong, C.c_int, C.c_int]

@@ -1,18 +1,14 @@
 """Shared by tests/test_getup_device_cpu.py and tests/test_getup_device_gpu.py: the host build of phc_amd/csrc/phc_getup.h (tests/getup_shim.cpp, g++), the
 caller-side state of one phc_getup_assign launch in host memory with guard words behind every array, and a numpy restatement of
 HumanoidImGetup._reset_envs (phc_amd/env/tasks/humanoid_im_getup.py) fed with explicit uniforms and an explicit permutation -- the oracle of the rules."""
-import atexit
 import copy
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD_WORDS = 16      # bytes-wise: 16 elements of the array's own type behind every array
 GUARD_BYTE = 0x5A
 KEY = 0x1234ABCD5678EF01
@@ -32,13 +28,7 @@ OUTPUTS = ("root_states", "dof_state", "avail", "assign", "recovery_counter", "k
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="getup_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "getup_shim.so")
-    # the flags of phc_getup.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "getup_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("getup_shim.cpp", "phc_getup.hip")
     for name, args, res in (("getup_sizeof_args", [], C.c_int), ("getup_block", [], C.c_int), ("getup_max_envs", [], C.c_int),
                             ("getup_draws_batch", [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_void_p], None),
                             ("getup_perm_of", [C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p], None),

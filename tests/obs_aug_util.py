@@ -2,18 +2,14 @@
 state of one phc_obs_augment / phc_occl_advance launch in host memory with guard elements behind every array, and two oracles: a numpy restatement of
 HumanoidIm._fut_dropout + _add_obs_noise and of _update_occl_training (phc_amd/env/tasks/humanoid_im.py) fed with explicit uniforms / normals -- the oracle of
 the rules -- and an fp64 Box-Muller on the same 24-bit integers -- the oracle of the noise values."""
-import atexit
 import copy
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD = 16            # guard elements of the array's own type behind every array
 GUARD_BYTE = 0x5A
 KEY = 0x0F1E2D3C4B5A6978
@@ -33,13 +29,7 @@ OCCL_N, OCCL_J = (1, 63, 64, 65, 257), (1, 9, 24, 25, 64)
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="obs_aug_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "obs_aug_shim.so")
-    # the flags of phc_obs_aug.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "obs_aug_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("obs_aug_shim.cpp", "phc_obs_aug.hip")
     p, i32, i64, u64, f = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
     for name, args, res in (("obs_aug_sizeof_args", [], C.c_int), ("obs_aug_block", [], C.c_int), ("obs_aug_max_obs", [], C.c_int),
                             ("obs_aug_max_samples", [], C.c_int), ("occl_max_bodies", [], C.c_int),

@@ -2,18 +2,14 @@
 numpy-backed caller of it with the state layout of phc_proj_args_t and guard words behind every array, posed body states, and `Oracle`: the rules of
 include/phc_amd.h (phc_proj_advance) stated in fp64 numpy, from the rules and not from the header's code.  The oracle takes the uniforms of the draws
 from the host build (they are exact fp32 numbers; their law is tested on its own) and the same fp32 inputs, upcast."""
-import atexit
 import ctypes as C
 import functools
 import math
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD = 0x5A5A5A5A   # int32 guard word; as float bits 1.5e16
 PAD = 16
 INT_NAMES = ("life", "countdown", "thrown", "hits", "last_hit")
@@ -23,13 +19,7 @@ U32 = 2.0 ** -24     # fp32 unit round-off
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="proj_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "proj_shim.so")
-    # the flags of phc_proj.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "proj_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("proj_shim.cpp", "phc_proj.hip")
     lib.proj_draws_batch.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
     lib.proj_draws_batch.restype = None
     lib.proj_args_check_of.argtypes = [C.POINTER(L.ProjArgs)]

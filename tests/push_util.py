@@ -1,29 +1,19 @@
 """Shared by tests/test_push_device_cpu.py and tests/test_push_device_gpu.py: the host build of phc_amd/csrc/phc_push.h (tests/push_shim.cpp, g++) and a
 numpy-backed caller of it with the state layout of phc_push_args_t."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD = 0x5A5A5A5A   # int32 guard word; as float bits 1.5e16
 
 
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="push_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "push_shim.so")
-    # the flags of phc_push.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "push_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("push_shim.cpp", "phc_push.hip")
     lib.push_draws_batch.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_void_p]
     lib.push_draws_batch.restype = None
     lib.push_args_check_of.argtypes = [C.POINTER(L.PushArgs)]

@@ -2,17 +2,13 @@
 caller-side state of a phc_motion_record launch in host memory with guard elements behind every array, constructed simulator states for the three model
 families, and two oracles: a numpy statement of the row rule (which row goes where, the header, the four counters -- exact) and an fp64 statement of a row's
 computed columns (the root's exp map, the robots' axis x angle rows) on the same fp32 data."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD = 16            # guard elements of the array's own type behind every array
 F = np.float32
 DT = F(1 / 30)
@@ -30,13 +26,7 @@ OVER = {"smpl": (), "h1": ("robot=unitree_h1", "env=env_im_h1_phc", "sim=robot_s
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="record_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "record_shim.so")
-    # the flags of phc_record.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "record_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("record_shim.cpp", "phc_record.hip")
     pm, pa = C.POINTER(L.Model), C.POINTER(L.MotionRecordArgs)
     for name, args, res in (("record_sizeof_args", [], C.c_int), ("record_block", [], C.c_int), ("record_width_of", [C.c_int] * 4, C.c_int),
                             ("record_group_of", [C.c_int] * 2, C.c_int), ("motion_record_check_of", [pm, pa], C.c_int), ("motion_record_host_of", [pm, pa], None)):

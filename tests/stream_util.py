@@ -1,15 +1,11 @@
 """TEST INFRASTRUCTURE shared by tests/test_stream_cpu.py and tests/test_stream_gpu.py: the host build of phc_amd/csrc/phc_stream.h (tests/stream_shim.cpp,
 g++), a numpy-backed caller with the layout of phc_stream_args_t, seeded keypoint streams and body states of any shape, and a fp64 numpy restatement of the
 launch that filters with scipy's own gaussian_filter1d (the kernel's folded table never enters it)."""
-import atexit
 import collections
 import ctypes as C
 import functools
 import json
 import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 from scipy.ndimage import gaussian_filter1d
@@ -18,6 +14,7 @@ from phc_amd import _lib as L
 from phc_amd import abi
 from phc_amd import stream as S
 from teleop_util import TOL   # |a - b| <= TOL max(1, |b|): the bound of the post-physics floats
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -27,13 +24,7 @@ STATE = ("ring_body", "ring_root", "head", "count", "has_prev", "cur_ref", "cur_
 
 @functools.lru_cache(maxsize=None)
 def shim():
-    d = tempfile.mkdtemp(prefix="stream_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "stream_shim.so")
-    # the flags of phc_stream.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "stream_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("stream_shim.cpp", "phc_stream.hip")
     for fn in (lib.stream_args_check_of, lib.stream_track_host):
         fn.argtypes = [C.POINTER(L.Model), C.POINTER(L.ImParams), C.POINTER(L.StreamArgs)]
         fn.restype = C.c_int

@@ -1,20 +1,14 @@
 """TEST INFRASTRUCTURE shared by tests/test_teleop_cpu.py and tests/test_teleop_gpu.py: the host build of phc_amd/csrc/phc_teleop.h (tests/teleop_shim.cpp,
 g++), a numpy-backed caller with the layout of phc_teleop_args_t, a small motion library whose root velocity is prescribed frame by frame, seeded inputs of
 any shape, and the comparison at the project's bound for the post-physics floats."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 from phc_amd import _lib as L
 from phc_amd import abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 F = np.float32
 TERMS = L.TELEOP_TERMS
 TOL = 2e-5   # |a - b| <= TOL max(1, |b|): the bound of the post-physics floats
@@ -32,13 +26,7 @@ NEEDS = {"dof_pos_limits": ("dof_state", "dof_limits_lower", "dof_limits_upper")
 
 @functools.lru_cache(maxsize=None)
 def shim():
-    d = tempfile.mkdtemp(prefix="teleop_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "teleop_shim.so")
-    # the flags of phc_teleop.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "teleop_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("teleop_shim.cpp", "phc_teleop.hip")
     for fn in (lib.teleop_args_check_of, lib.teleop_rewards_host):
         fn.argtypes = [C.POINTER(L.MotionLib), C.POINTER(L.TeleopArgs)]
         fn.restype = C.c_int

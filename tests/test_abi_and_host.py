@@ -6,13 +6,12 @@
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "phc_amd.h")
@@ -34,22 +33,42 @@ def test_library_exports_every_declared_symbol():
     assert lib.phc_abi_version() == 37
 
 
-def test_struct_sizes_match_the_header():
-    """Compile a tiny C program against include/phc_amd.h and compare sizeof() with the ctypes mirrors."""
-    from phc_amd import _lib
-    names = {"phc_model_t": _lib.Model, "phc_motion_lib_t": _lib.MotionLib, "phc_sim_state_t": _lib.SimState,
-             "phc_sim_params_t": _lib.SimParams, "phc_im_params_t": _lib.ImParams, "phc_im_buffers_t": _lib.ImBuffers, "phc_ppo_params_t": _lib.PpoParams,
-             "phc_colsum_job_t": _lib.ColsumJob}
-    src = '#include <stdio.h>\n#include "phc_amd.h"\nint main(){' + "".join(f'printf("{n} %zu\\n", sizeof({n}));' for n in names) + "return 0;}"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "s")
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    for line in out.strip().splitlines():
-        n, sz = line.split()
-        assert C.sizeof(names[n]) == int(sz), f"{n}: ctypes {C.sizeof(names[n])} vs C {sz}"
+def _header_structs():
+    """name -> number of declared fields, for every `typedef struct { ... } phc_*_t;` of the header (comments stripped; a field is one declarator)."""
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return {name: sum(stmt.count(",") + 1 for stmt in body.split(";") if stmt.strip())
+            for body, name in re.findall(r"typedef struct \{(.*?)\}\s*(phc_\w+_t)\s*;", txt, flags=re.S)}
+
+
+def test_struct_layouts_and_constants_match_the_header():
+    """Every struct of include/phc_amd.h has one ctypes mirror in phc_amd/_lib.py (phc_foo_bar_t <-> FooBar) and the reverse; size, the offset of every
+    mirror field (by name) and the number of fields agree.  Equal sizes, equal offsets of every named field and equal counts leave no room for a swapped,
+    missing or extra field.  Every Python constant that restates a macro of the header equals the evaluated macro."""
+    from phc_amd import _lib as L
+    from phc_amd import abi
+    declared = _header_structs()
+    mirrors = {n: c for n, c in vars(L).items() if isinstance(c, type) and issubclass(c, C.Structure) and c.__module__ == L.__name__}
+    paired = {name: mirrors.get("".join(w.capitalize() for w in name[4:-2].split("_"))) for name in declared}
+    assert len(declared) >= 29
+    assert not [n for n, c in paired.items() if c is None], "header structs without a ctypes mirror"
+    assert not sorted(set(mirrors) - {c.__name__ for c in paired.values()}), "ctypes mirrors without a header struct"
+    want = {f"sizeof({n})": C.sizeof(c) for n, c in paired.items()}
+    want.update({f"offsetof({n}, {f})": getattr(c, f).offset for n, c in paired.items() for f, _ in c._fields_})
+    want.update({"PHC_MAX_BODIES": abi.MAX_BODIES, "PHC_RESET_SUBLISTS": abi.RESET_SUBLISTS, "PHC_RESET_COUNT_STRIDE": abi.RESET_COUNT_STRIDE,
+                 "PHC_RENDER_PALETTE": L.RENDER_PALETTE, "PHC_RENDER_MARKER_ID": L.RENDER_MARKER_ID, "PHC_RENDER_MAX_PIXELS": L.RENDER_MAX_PIXELS,
+                 "PHC_RENDER_MAX_SHAPES": L.RENDER_MAX_SHAPES, "PHC_RENDER_MAX_MARKERS": L.RENDER_MAX_MARKERS, "PHC_RENDER_MESH_ID": L.RENDER_MESH_ID,
+                 "PHC_RENDER_MAX_INSTANCES": L.RENDER_MAX_INSTANCES, "PHC_RENDER_MAX_TRIANGLES": L.RENDER_MAX_TRIANGLES,
+                 f"PHC_RENDER_MESH_MIN_CROSS == {L.RENDER_MESH_MIN_CROSS!r}f": 1,     # (a float: compared in C, as fp32)
+                 "PHC_PROJ_MAX_SLOTS": L.PROJ_MAX_SLOTS, "PHC_PROJ_MAX_SHAPES": L.PROJ_MAX_SHAPES, "PHC_PROJ_MAX_ROWSETS": L.PROJ_MAX_ROWSETS,
+                 "PHC_PROJ_SNAPSHOT": L.PROJ_SNAPSHOT, "PHC_PROJ_SELECT": L.PROJ_SELECT, "PHC_TELEOP_NUM_TERMS": len(L.TELEOP_TERMS),
+                 "PHC_TELEOP_MAX_FEET": L.TELEOP_MAX_FEET, "PHC_STREAM_MAX_WINDOW": L.STREAM_MAX_WINDOW, "PHC_STREAM_MAX_PAIRS": L.STREAM_MAX_PAIRS,
+                 "PHC_STREAM_ADVANCE": L.STREAM_ADVANCE, "PHC_STREAM_OBSERVE": L.STREAM_OBSERVE, "PHC_FIT_MAX_MATCHED": L.FIT_MAX_MATCHED,
+                 "PHC_RECORD_REF": L.RECORD_REF, "PHC_RECORD_SEED": L.RECORD_SEED, "PHC_RECORD_ONE_SEGMENT": L.RECORD_ONE_SEGMENT})
+    for bit, term in enumerate(L.TELEOP_TERMS):   # the bit of each term
+        want["PHC_TELEOP_" + {"feet_air_time_teleop": "FEET_AIR_TIME"}.get(term, term.upper())] = bit
+    bad = [f"{e}: header {h}, Python {m}" for (e, m), h in zip(want.items(), host_build.header_values(*want)) if h != m]
+    bad += [f"{n}: header declares {declared[n]} fields, mirror {len(c._fields_)}" for n, c in paired.items() if declared[n] != len(c._fields_)]
+    assert not bad, "\n".join(bad)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")

@@ -1,28 +1,22 @@
 """CPU checks of the evaluation sweep's device metric path: the 3x3 similarity solve of phc_amd/csrc/phc_eval.h (`eval_similarity`, the uniform
 part of `phc_eval_accumulate`'s Procrustes term), built for the host with g++ and compared against `im_eval._procrustes` (numpy SVD, fp64)."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 F = np.float32
 CLOUDS, POINTS = 200, 24
 
 
 @pytest.fixture(scope="module")
 def shim():
-    with tempfile.TemporaryDirectory() as d:
-        so = os.path.join(d, "eval_shim.so")
-        subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "eval_similarity_shim.cpp"), "-o", so], check=True)
-        lib = C.CDLL(so)
-        lib.eval_similarity_batch.argtypes = [C.c_int] + [C.c_void_p] * 4
-        lib.eval_similarity_batch.restype = None
-        yield lib
+    lib = host_build.shim("eval_similarity_shim.cpp", "phc_eval.hip")
+    lib.eval_similarity_batch.argtypes = [C.c_int] + [C.c_void_p] * 4
+    lib.eval_similarity_batch.restype = None
+    return lib
 
 
 def _clouds(noise, seed):

@@ -4,14 +4,13 @@ trajectory against `fit_clip(dtype=float64)`, and the bits under segmenting and 
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 import fit_util as U
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["chain3", "unitree_h1", "unitree_g1"]
@@ -29,11 +28,7 @@ def test_abi_names_struct_size_and_version():
     declared = set(re.findall(r"^int(?:32|64)_t\s+(phc_\w+)\s*\(", header, flags=re.M))
     for name in ("phc_fit_scratch_bytes", "phc_fit_iterate"):
         assert name in L.EXPORTED_SYMBOLS and name in declared
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write('#include <stdio.h>\n#include "phc_amd.h"\nint main(){printf("%zu %d\\n", sizeof(phc_fit_args_t), PHC_FIT_MAX_MATCHED);return 0;}')
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")], check=True)
-        size, max_matched = map(int, subprocess.run([os.path.join(d, "s")], check=True, capture_output=True, text=True).stdout.split())
-    assert size == C.sizeof(L.FitArgs) and max_matched == L.FIT_MAX_MATCHED
+    # (phc_fit_args_t and PHC_FIT_MAX_MATCHED against their mirrors: tests/test_abi_and_host.py)
     assert [f[0] for f in L.FitArgs._fields_ if f[1] is C.c_void_p] == list(POINTERS)
     lib = L.load()
     assert lib.phc_abi_version() == 37
@@ -343,3 +338,14 @@ def test_butterfly_order_and_taps():
     x[4] = 1.0
     np.testing.assert_allclose(taps, gaussian_filter_time(x)[2:7, 0].numpy(), rtol=2 ** -23)
     assert lib.fit_tile_frames_of(23) == 8 and lib.fit_tile_frames_of(32) == 8 and lib.fit_tile_frames_of(33) == 4
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------
+# the sanitizer program
+
+def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers():
+    """tests/fit_asan_main.cpp (its own main; nothing is loaded into Python): a 3-body chain with an extended body and a 34-body chain, clips of 1, 2 and 9
+    frames, on heap arrays of exact size."""
+    returncode, stdout, stderr = host_build.run_sanitized("fit_asan_main.cpp")
+    print(stdout[-2000:], stderr)
+    assert returncode == 0 and stdout.strip().endswith("ok"), stdout + stderr

@@ -12,9 +12,10 @@ import pytest
 import torch
 
 import fit_sph_util as S
+import host_build
 import test_fit_device_cpu as T0      # the update's expected value and bound, the placements: shared with the revolute fit's tests
 
-ROOT = S.ROOT
+ROOT = host_build.ROOT
 GRAD_FLOOR = 0.0     # see test_gradient_on_constructed_states
 POINTERS = tuple(p for p in T0.POINTERS if p != "axis")
 
@@ -384,3 +385,11 @@ def test_cli_writes_a_library(tmp_path):
     fit_keypoints.main(["--joints", str(tmp_path / "kp.npz"), "--out", str(tmp_path / "clips.pkl"), "--iterations", "2"])
     out = joblib.load(tmp_path / "clips.pkl")
     assert list(out) == ["a", "b"] and out["a"]["fps"] == 30 and out["b"]["fps"] == 60 and out["b"]["pose_quat_global"].shape == (7, 24, 4)
+
+
+def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers():
+    """tests/fit_sph_asan_main.cpp (its own main; nothing is loaded into Python): a 4-body tree, a 1-body model and a 32-body chain, clips of 1, 2 and 9
+    frames, on heap arrays of exact size with a null `axis`."""
+    returncode, stdout, stderr = host_build.run_sanitized("fit_sph_asan_main.cpp")
+    print(stdout[-2000:], stderr)
+    assert returncode == 0 and stdout.strip().endswith("ok"), stdout + stderr

@@ -7,13 +7,12 @@
   5. the stand-alone sanitizer program (tests/getup_asan_main.cpp)"""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import getup_util as gu
+import host_build
 
 PROBS = (0.0, 0.5, 1.0)
 
@@ -248,12 +247,8 @@ def test_stream_keys_of_one_seed_are_apart():
 
 
 # ---- 5. the sanitizer program ------------------------------------------------------------------------------------------------------------------------
-def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers(tmp_path):
+def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers():
     """tests/getup_asan_main.cpp (its own main; nothing is loaded into Python): the tight pool and the out-of-range assign at N = 65 and 1025."""
-    exe = str(tmp_path / "getup_asan")
-    # (the sanitizer runtimes linked statically: the program does not depend on the order of the process's shared libraries)
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-ffp-contract=off", "-std=c++17", "-I",
-                    os.path.join(gu.ROOT, "phc_amd", "csrc"), os.path.join(gu.ROOT, "tests", "getup_asan_main.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout, r.stderr)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    returncode, stdout, stderr = host_build.run_sanitized("getup_asan_main.cpp")
+    print(stdout, stderr)
+    assert returncode == 0 and stdout.strip().endswith("ok"), stdout + stderr

@@ -8,8 +8,6 @@
   6. the refusals
   7. the stand-alone sanitizer program (tests/record_asan_main.cpp)"""
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
@@ -18,6 +16,7 @@ import torch
 
 import record_util as ru
 from phc_amd import _lib as L
+import host_build
 
 F = np.float32
 
@@ -298,12 +297,8 @@ def test_without_the_switch_nothing_is_recorded(tmp_path):
 
 
 # ---- 7. the sanitizer program ----------------------------------------------------------------------------------------------------------------------------
-def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers(tmp_path):
+def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers():
     """tests/record_asan_main.cpp (its own main; nothing is loaded into Python): the overflow and N = 65 cases on heap arrays of exact size."""
-    exe = str(tmp_path / "record_asan")
-    # (the sanitizer runtimes linked statically: the program does not depend on the order of the process's shared libraries)
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-ffp-contract=off", "-std=c++17", "-I",
-                    os.path.join(ru.ROOT, "phc_amd", "csrc"), os.path.join(ru.ROOT, "tests", "record_asan_main.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-2000:], r.stderr)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    returncode, stdout, stderr = host_build.run_sanitized("record_asan_main.cpp")
+    print(stdout[-2000:], stderr)
+    assert returncode == 0 and stdout.strip().endswith("ok"), stdout + stderr

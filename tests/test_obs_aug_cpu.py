@@ -10,13 +10,12 @@ g++ (tests/obs_aug_shim.cpp, tests/obs_aug_util.py).
 
 Measured on the host build (glibc logf / sinf / cosf): the largest error of a noised element over every case below is 0.46 of its bound E (obs_aug_util.noise_bound)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import obs_aug_util as ou
+import host_build
 
 
 def _id_lists(n):
@@ -261,13 +260,9 @@ def test_the_options_in_the_host_phases(switch):
 
 
 # ---- 5. the sanitizer program ------------------------------------------------------------------------------------------------------------------------
-def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers(tmp_path):
+def test_host_build_runs_clean_under_the_address_and_undefined_sanitizers():
     """tests/obs_aug_asan_main.cpp (its own main; nothing is loaded into Python): the cases' shapes in all three selection forms and the occlusion schedule,
     on heap arrays of exact size."""
-    exe = str(tmp_path / "obs_aug_asan")
-    # (the sanitizer runtimes linked statically: the program does not depend on the order of the process's shared libraries)
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-ffp-contract=off", "-std=c++17", "-I",
-                    os.path.join(ou.ROOT, "phc_amd", "csrc"), os.path.join(ou.ROOT, "tests", "obs_aug_asan_main.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-2000:], r.stderr)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    returncode, stdout, stderr = host_build.run_sanitized("obs_aug_asan_main.cpp")
+    print(stdout[-2000:], stderr)
+    assert returncode == 0 and stdout.strip().endswith("ok"), stdout + stderr

@@ -12,12 +12,12 @@ flight of L env steps the random run takes K L.  Worst measured (printed by ever
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import proj_util as pu
+import host_build
 
 ROBOTS = ["smpl_humanoid", "g1_humanoid"]
 R, G, DT, S = 0.1, -9.81, 1 / 30, 8
@@ -450,7 +450,7 @@ def test_binding_types():
     assert L.ProjArgs.key.offset % 8 == 0 and L.ProjArgs.env_offset.offset == L.ProjArgs.key.offset + 8 and L.ProjArgs.bodies.offset == L.ProjArgs.key.offset + 16
     assert C.sizeof(L.ProjArgs) == L.ProjArgs.bodies.offset + 19 * 8
     import re
-    header = open(os.path.join(pu.ROOT, "include", "phc_amd.h")).read()
+    header = open(os.path.join(host_build.ROOT, "include", "phc_amd.h")).read()
     body = header[header.index("#define PHC_PROJ_MAX_SLOTS"):header.index("} phc_proj_args_t;")]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     at = [re.search(rf"[\s*]{n}[,;]", body).start() for n in names]
@@ -522,15 +522,12 @@ def test_rows_snapshot_and_select_on_the_host():
 
 
 # ---- stand-alone sanitizer program ------------------------------------------------------------------------------------------------------------------------------
-def test_stand_alone_sanitizer_program(tmp_path):
+def test_stand_alone_sanitizer_program():
     """tests/proj_asan_main.cpp (its own main; nothing is loaded into Python): N = 65 envs and the corner cases on heap arrays of exact size, under
     AddressSanitizer and UndefinedBehaviorSanitizer."""
-    exe = str(tmp_path / "proj_asan")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-I",
-                    os.path.join(pu.ROOT, "phc_amd", "csrc"), os.path.join(pu.ROOT, "tests", "proj_asan_main.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-2000:], r.stderr[-4000:])
-    assert r.returncode == 0 and "proj_asan: ok" in r.stdout
+    returncode, stdout, stderr = host_build.run_sanitized("proj_asan_main.cpp")
+    print(stdout[-2000:], stderr[-4000:])
+    assert returncode == 0 and "proj_asan: ok" in stdout
 
 
 # ---- random run ------------------------------------------------------------------------------------------------------------------------------------------------------

@@ -1,18 +1,12 @@
 """The device push schedule (`+perturb.rng=device`, phc_push_advance) on a machine without a GPU: phc_amd/csrc/phc_push.h built for the host with g++
 (tests/push_shim.cpp).  Its transition against `PushSchedule` under the same uniforms, its draws, the whole host path's structure, the guards and
 the binding."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
 import numpy as np
 import pytest
 import torch
 
 import push_util as pu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["Pelvis", "L_Hip", "Torso", "Head"]   # tests/test_ext_wrench_cpu.py::_schedule: 16 envs, pause 6 .. 12 steps, duration 3
 N, DT, SEED, STEPS = 16, 1 / 30, 5, 100
 FORCE_TOL = 1e-3   # newtons.  At 400 N one fp32 ulp is 3e-5 N; cosf / sinf against torch's cos / sin differ by a few ulp
@@ -172,14 +166,7 @@ def test_binding_and_struct_size():
     from phc_amd import _lib as L
     assert "phc_push_advance" in L.EXPORTED_SYMBOLS
     fn = L.load().phc_push_advance
-    assert len(fn.argtypes) == 2 and fn.restype is L.c_i32
-    src = '#include <stdio.h>\n#include "phc_amd.h"\nint main(){printf("%zu\\n", sizeof(phc_push_args_t));return 0;}'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "s")], check=True)
-        out = subprocess.run([os.path.join(d, "s")], check=True, capture_output=True, text=True).stdout
-    assert C.sizeof(L.PushArgs) == int(out)
+    assert len(fn.argtypes) == 2 and fn.restype is L.c_i32   # (phc_push_args_t against its mirror: tests/test_abi_and_host.py)
 
 
 def test_argument_checks():

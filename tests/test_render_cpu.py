@@ -3,12 +3,10 @@
   * the exclusion cap (at most 2 % of a view's pixels) on every committed test scene, and the 5 degree rule of their cameras;
   * a write_png round trip decoded with zlib;
   * the follow camera against the reference's _init_camera / _update_camera (humanoid.py:1715-1743);
-  * the ctypes mirrors of phc_camera_t / phc_render_scene_t against sizeof() from a C program."""
-import ctypes as C
+  * the values of the renderer's header limits (the struct layouts: tests/test_abi_and_host.py)."""
 import math
 import os
 import struct
-import subprocess
 import tempfile
 import zlib
 
@@ -16,8 +14,7 @@ import numpy as np
 import pytest
 
 import render_oracle as ro
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 
 
 def _style():
@@ -162,25 +159,8 @@ def test_follow_camera_reproduces_the_reference_placement():
 
 
 def test_render_struct_sizes_match_the_header():
+    """The layouts themselves: tests/test_abi_and_host.py.  Here: the values the renderer's oracle and its documented limits rest on."""
     from phc_amd import _lib
-    names = {"phc_camera_t": _lib.Camera, "phc_render_scene_t": _lib.RenderScene}
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "phc_amd.h"\nint main(){' + "".join(f'printf("{n} %zu\\n", sizeof({n}));' for n in names)
-    fields = [f for f, _ in _lib.RenderScene._fields_]
-    src += "".join(f'printf("off {f} %zu\\n", offsetof(phc_render_scene_t, {f}));' for f in fields) + "return 0;}"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "s")
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    for line in out.strip().splitlines():
-        a, b, sz = line.split() if line.startswith("off") else (None,) + tuple(line.split())
-        if a is None:
-            assert C.sizeof(names[b]) == int(sz), f"{b}: ctypes {C.sizeof(names[b])} vs C {sz}"
-        else:
-            assert getattr(_lib.RenderScene, b).offset == int(sz), b
     assert _lib.RENDER_PALETTE == 16 and _lib.RENDER_MARKER_ID == ro.MARKER_ID
-    hdr = open(os.path.join(ROOT, "include", "phc_amd.h")).read()
-    for k, v in (("PHC_RENDER_MAX_PIXELS", "(1 << 24)"), ("PHC_RENDER_MAX_SHAPES", "128"), ("PHC_RENDER_MAX_MARKERS", "128"),
-                 ("PHC_RENDER_PALETTE", "16"), ("PHC_RENDER_MARKER_ID", "1000")):
-        assert f"#define {k} {v}" in hdr
+    assert host_build.header_values("PHC_RENDER_MAX_PIXELS", "PHC_RENDER_MAX_SHAPES", "PHC_RENDER_MAX_MARKERS", "PHC_RENDER_PALETTE",
+                                    "PHC_RENDER_MARKER_ID") == [1 << 24, 128, 128, 16, 1000]

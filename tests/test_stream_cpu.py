@@ -8,9 +8,6 @@
      (second lane round), both joint orders and up axes, remove_base_rot, the broadcast row, a restart of some envs mid-run, the observe mode;
   5. HumanoidImDemo.host_only: defaults, every refusal and option error by its message; the names parse_task knows."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -20,7 +17,6 @@ import stream_util as su
 from phc_amd import _lib as L
 from phc_amd import stream as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 EINVAL, EUNSUPPORTED = -1, -2
 MARGIN = 1e-3
@@ -35,14 +31,7 @@ def gold(golden):
 def test_symbol_version_and_struct_size():
     lib = L.load()
     assert "phc_stream_track" in L.EXPORTED_SYMBOLS and hasattr(lib, "phc_stream_track")
-    assert lib.phc_abi_version() == 37
-    src = '#include <stdio.h>\n#include "phc_amd.h"\nint main(){printf("%zu %d %d", sizeof(phc_stream_args_t), PHC_STREAM_MAX_WINDOW, PHC_STREAM_MAX_PAIRS);return 0;}'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "s")], check=True)
-        size, window, pairs = (int(v) for v in subprocess.run([os.path.join(d, "s")], check=True, capture_output=True, text=True).stdout.split())
-    assert C.sizeof(L.StreamArgs) == size and (window, pairs) == (L.STREAM_MAX_WINDOW, L.STREAM_MAX_PAIRS)
+    assert lib.phc_abi_version() == 37   # (phc_stream_args_t and the PHC_STREAM_* macros against their mirrors: tests/test_abi_and_host.py)
 
 
 def _checked(n=2, nb=24, **edit):

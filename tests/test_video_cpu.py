@@ -5,13 +5,13 @@ import ctypes as C
 import io
 import os
 import struct
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
 import video_util as vu
+import host_build
 
 
 def _lib():
@@ -190,15 +190,12 @@ def test_no_frames_is_no_work_and_huge_frames_are_unsupported():
     assert lib.phc_jpeg_encode(C.byref(a), None) == -2, "a frame bound above 2^31 - 1"
 
 
-def test_host_sanitizer_program(tmp_path):
+def test_host_sanitizer_program():
     """tests/jpeg_asan_main.cpp (its own main; nothing is loaded into Python): the longest-coding inputs on heap arrays of exact size, under AddressSanitizer
     and UndefinedBehaviorSanitizer."""
-    exe = str(tmp_path / "jpeg_asan")
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-I",
-                    os.path.join(vu.ROOT, "phc_amd", "csrc"), os.path.join(vu.ROOT, "tests", "jpeg_asan_main.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-2000:], r.stderr[-4000:])
-    assert r.returncode == 0 and "jpeg_asan: ok" in r.stdout
+    returncode, stdout, stderr = host_build.run_sanitized("jpeg_asan_main.cpp")
+    print(stdout[-2000:], stderr[-4000:])
+    assert returncode == 0 and "jpeg_asan: ok" in stdout
 
 
 # ---------------------------------------------------------------------------------------------------------------- Pillow

@@ -5,18 +5,14 @@ documents and not from phc_jpeg.h or phc_amd/video.py:
   (b) `decode`      a baseline entropy decoder (Annex F): markers, DQT / DHT / DRI, RSTn, byte unstuffing -> the quantised coefficients;
   (c) `read_avi`    a RIFF walker for the AVI files.
 The test images and the constructed blocks live here too, so that the CPU and the GPU tests run the same cases under the same rules."""
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 GUARD, PAD = 0xA5, 64
 U32 = 2.0 ** -24     # fp32 unit round-off
 
@@ -24,13 +20,7 @@ U32 = 2.0 ** -24     # fp32 unit round-off
 @functools.lru_cache(maxsize=None)
 def shim():
     from phc_amd import _lib as L
-    d = tempfile.mkdtemp(prefix="jpeg_shim_")
-    atexit.register(shutil.rmtree, d, ignore_errors=True)
-    so = os.path.join(d, "jpeg_shim.so")
-    # the flags of phc_jpeg.hip's entry in phc_amd/build.py: no contraction, no fast-math
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "phc_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "jpeg_shim.cpp"), "-o", so], check=True)
-    lib = C.CDLL(so)
+    lib = host_build.shim("jpeg_shim.cpp", "phc_jpeg.hip")
     lib.jpeg_args_check_of.argtypes = [C.POINTER(L.JpegArgs)]
     lib.jpeg_encode_host.argtypes = [C.POINTER(L.JpegArgs)]
     lib.jpeg_frame_bound_of.argtypes = [C.c_int, C.c_int, C.c_int]
